@@ -16,11 +16,17 @@ the same steps with the whole text reassembled on rank 0 in strcmp order by
 bg_group_gather (bedops_amd/csrc/bg_group.hip: grouped ncclSend/ncclRecv over xGMI) are
 timed beside them (`multi_gpu`: placement vs with-gather step time, the gather's cost).
 Strong scaling by default: the dataset is the fixed 100M x 100M at every N (`--weak`: N x
-100M rows per file). After the timed steps rank 0 hashes the reassembled output against the
-reference binary's hash at every N.
+100M rows per file). With `--full`, after the timed steps rank 0 hashes the reassembled output
+against the reference binary's hash at every N.
 
-Rank 0, N = 1, also times, all file -> file with the inputs
-in the page cache and the output written to a file:
+A plain run (`--gpus N --steps K --warmup W`) does only that: it generates the inputs, warms
+up, times the K steps and prints the result line. `--dump-outputs DIR` also writes what the
+last timed step returned (dump_outputs()). Everything below runs only with `--full`: the
+per-kernel tables and the dominant kernel's roofline, the with-gather steps at N > 1, the
+parity hash, the file -> file CLI and the CPU baselines.
+
+With `--full` rank 0, N = 1, also times, all file -> file with
+the inputs in the page cache and the output written to a file:
   e2e           the drop-in CLI `bedops_amd/bin/bedops --intersect A B > out` (process start,
                 HIP init, reads, device work, output write), median of 3, with the
                 BEDGPU_STATS phase marks of the median run; `--e2e-devices 0,1,..` also times
@@ -467,6 +473,45 @@ def cpu_fanout_ref(L, W, paths, rows, td, workers, runs):
                       f"median of {runs}"}
 
 
+# ----------------------------------------------------------------------------- outputs
+DUMP_BLOCK = 1 << 16     # bytes per block sum and per sampled window
+DUMP_WINDOWS = 128       # 128 x 64 KiB = 8 MiB of text -> 32 MiB of float32
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirpath, rows, text, suffix=""):
+    """--dump-outputs: what the last timed step handed to its caller, the row count and the
+    sorted BED text, as arrays that two builds can be compared by:
+      counts.npy               float64 [rows, bytes]
+      text_block_sums.npy      float64, the byte sum of every consecutive 64 KiB block of the
+                               text (every output byte is counted once)
+      text_sample.npy          float32, the text's bytes: all of them up to 8 MiB, else 128
+                               windows of 64 KiB (the first, the last and 126 at offsets drawn
+                               from a fixed seed), concatenated in offset order
+      text_sample_offsets.npy  float64, the byte offset of each window
+    (suffix: `_rank<r>` at N > 1, where each rank writes its own chromosomes' text)"""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    b = np.frombuffer(text, dtype=np.uint8)
+    n = len(b)
+    full = n // DUMP_BLOCK * DUMP_BLOCK
+    sums = b[:full].reshape(full // DUMP_BLOCK, DUMP_BLOCK).sum(axis=1, dtype=np.uint32).astype(np.float64)
+    if full < n:
+        sums = np.append(sums, float(b[full:].sum(dtype=np.uint32)))
+    if n <= DUMP_WINDOWS * DUMP_BLOCK:
+        offs, sample = np.zeros(1, dtype=np.int64), b
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        mid = rng.integers(0, n - DUMP_BLOCK, size=DUMP_WINDOWS - 2)
+        offs = np.sort(np.concatenate([[0, n - DUMP_BLOCK], mid])).astype(np.int64)
+        sample = np.concatenate([b[o:o + DUMP_BLOCK] for o in offs])
+    for name, arr in (("counts", np.array([rows, n], dtype=np.float64)),
+                      ("text_block_sums", sums),
+                      ("text_sample", sample.astype(np.float32)),
+                      ("text_sample_offsets", offs.astype(np.float64))):
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), arr)
+
+
 # ----------------------------------------------------------------------------- main
 def main():
     ap = argparse.ArgumentParser()
@@ -478,6 +523,14 @@ def main():
                     help="weak scaling: N x the workload's rows per file (default: strong)")
     ap.add_argument("--scale", type=float, default=1.0,
                     help="rows per input = scale x the workload's size (tests/smoke)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-kernel "
+                         "tables and the dominant kernel's roofline, the with-gather steps at N > 1, "
+                         "the parity hash, the file -> file CLI (e2e) and the CPU baselines (the "
+                         "--no-* and --cpu-*/--e2e-* options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (row count, "
+                         "sorted BED text: block sums and a fixed sample) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
@@ -498,6 +551,10 @@ def main():
                     help="(rehearsal of N > 1 on a one-GPU box) every rank on cuda:0, no RCCL "
                          "between ranks: the placement steps only, no gather, no parity hash")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.load_only:
+        ap.error("--dump-outputs: the loader stage alone returns no output")
     W = WORKLOADS[args.workload]
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -553,12 +610,14 @@ def main():
     state = {}
     inputs = [((t.data_ptr(), nb), k) for t, nb, k in zip(bufs, texts, W["kinds"])]
 
-    def step(gather=False):
+    def step(gather=False, hold=False):
         """one pass of the hot path. N > 1: each rank loads, operates and formats its
         chromosomes (the text stays in its HBM, as at N = 1) and the ranks exchange their
         per-chromosome byte counts, which places every rank's spans in the sorted output (what
         the sharded drop-in writes in place with per-device pwrite, cli_shard.h); gather=True
-        also reassembles the whole text on rank 0 over RCCL (bg_group_gather)"""
+        also reassembles the whole text on rank 0 over RCCL (bg_group_gather); hold=True
+        leaves the step's result and input set alive in state["held"] (--dump-outputs reads
+        the text after the clock has stopped)"""
         s = eng.load(inputs)
         if args.load_only:
             state["out_rows"] = state["out_bytes"] = 0
@@ -589,6 +648,9 @@ def main():
         elif "keep" in state:
             state["text"] = r.text()
             del state["keep"]
+        if hold:
+            state["held"] = (r, s)
+            return
         r.free()
         s.free()
 
@@ -608,34 +670,45 @@ def main():
     # dominant kernel (the first carries code-object loading and first-touch costs — with
     # --warmup 1 it named k_fmt_write, whose first launch faults its output pages in — so at
     # least two untimed steps run)
-    eng.prof_enable("*")
+    # a plain run warms up the same number of steps, unprofiled
+    first = last = dominant = None
+    comps = 0
+    if args.full:
+        eng.prof_enable("*")
     for w in range(max(args.warmup, 2)):
         step()
-        last = eng.prof_read()
-        eng.prof_enable("*")  # (clears the statistics)
-        if w == 0:
-            first = last
-    eng.prof_enable("")
-    dominant = max(last.items(), key=lambda kv: kv[1][1])[0]
-    comps = 0
-    if args.workload == "intersect":  # component counts size the merge/intersect kernels
-        s = eng.load(inputs)
-        for f in (0, 1):
-            m = eng.op("-m", s, [f])
-            comps += m.rows()
-            m.free()
-        s.free()
-    eng.prof_enable("*" if args.profile_all else dominant)
+        if args.full:
+            last = eng.prof_read()
+            eng.prof_enable("*")  # (clears the statistics)
+            if w == 0:
+                first = last
+    if args.full:
+        eng.prof_enable("")
+        dominant = max(last.items(), key=lambda kv: kv[1][1])[0]
+        if args.workload == "intersect":  # component counts size the merge/intersect kernels
+            s = eng.load(inputs)
+            for f in (0, 1):
+                m = eng.op("-m", s, [f])
+                comps += m.rows()
+                m.free()
+            s.free()
+    if args.full or args.profile_all:
+        eng.prof_enable("*" if args.profile_all else dominant)
     barrier()
     t_start = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(hold=bool(args.dump_outputs) and i == args.steps - 1)
     eng.sync()
     torch.cuda.synchronize(dev)
     t_end = time.perf_counter()
     if dist:
         dist.barrier()
     elapsed = t_end - t_start
+    if args.dump_outputs:  # the last timed step's own result, read after the clock stopped
+        r, s = state.pop("held")
+        dump_outputs(args.dump_outputs, r.rows(), r.text(), f"_rank{rank}" if world > 1 else "")
+        r.free()
+        s.free()
     total_rows = sum(rows)
     if dist:
         et = torch.tensor([elapsed], dtype=torch.float64)
@@ -644,11 +717,11 @@ def main():
         rt = torch.tensor([sum(rows)], dtype=torch.int64)
         dist.all_reduce(rt)
         total_rows = int(rt.item())
-    prof = eng.prof_read()
+    prof = eng.prof_read() if (args.full or args.profile_all) else {}
     # N > 1: the same steps with the whole text reassembled on rank 0 (the RCCL gather the
     # drop-in's pipe output needs), timed the same way, reported beside the placement steps
     multi = None
-    if dist and not args.load_only and not args.share_device:
+    if args.full and dist and not args.load_only and not args.share_device:
         barrier()
         g0 = time.perf_counter()
         for _ in range(args.steps):
@@ -673,7 +746,8 @@ def main():
 
     # parity after timing: the reassembled output against the reference hash, at every N
     verify = None
-    if not args.no_verify and not args.load_only and args.scale == 1.0 and not args.weak and not args.share_device:
+    if args.full and not args.no_verify and not args.load_only and args.scale == 1.0 and not args.weak \
+            and not args.share_device:
         if rank == 0:
             state["keep"] = True
         step()
@@ -698,7 +772,7 @@ def main():
     sizes = {"texts": texts, "rows": rows, "kinds": W["kinds"], "out": state["out_rows"],
              "out_bytes": state["out_bytes"], "comps": comps}
     roof = None
-    per_launch = kernel_bytes(dominant, sizes)
+    per_launch = kernel_bytes(dominant, sizes) if args.full else None
     if per_launch is not None and dominant in prof:
         calls, ms = prof[dominant]  # launches inside the timed region only
         avg_s = ms / 1e3 / max(calls, 1)
@@ -735,7 +809,7 @@ def main():
         grp.close()
         grp = None
         dist.barrier()
-        if not args.no_e2e and args.scale == 1.0 and not args.load_only and not args.weak \
+        if args.full and not args.no_e2e and args.scale == 1.0 and not args.load_only and not args.weak \
                 and not args.share_device:
             with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR")) as td:
                 paths, nrows = write_inputs(L, W, td)
@@ -745,7 +819,7 @@ def main():
                     e2e_sh["matches_reference"] = e2e_sh["output_sha16"] == W["ref"]["sha16"]
                 for p in paths:
                     os.unlink(p)
-    if world == 1 and args.scale == 1.0 and not args.load_only and (
+    if args.full and world == 1 and args.scale == 1.0 and not args.load_only and (
             not args.no_e2e or not args.no_cpu_baseline):
         with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR")) as td:
             paths, nrows = write_inputs(L, W, td)
@@ -827,9 +901,10 @@ def main():
         "parity": verify,
         "multi_gpu": multi,
         "kernels_first_step_ms": {k: round(v[1], 4) for k, v in
-                                  sorted(first.items(), key=lambda kv: -kv[1][1])},
+                                  sorted(first.items(), key=lambda kv: -kv[1][1])} if args.full else None,
         "kernels_warm_step_ms": {k: round(v[1], 4) for k, v in
-                                 sorted(last.items(), key=lambda kv: -kv[1][1])},
+                                 sorted(last.items(), key=lambda kv: -kv[1][1])} if args.full else None,
+        "full": args.full,
     }
     if args.profile_all:  # HIP-event time per timed step of every kernel
         line["kernels_ms_per_step"] = {k: round(v[1] / args.steps, 4) for k, v in

@@ -5,7 +5,7 @@ O=gpurun_out/r05_abp; mkdir -p $O
 for n in ${NAMES:-cur gtxt0}; do
   L=build/ab/$n/libbedgpu.so
   for k in 1 2; do
-    BEDGPU_LIB=$L timeout -k 10 200 python3 bench.py --load-only --steps 6 --warmup 1 --no-verify --no-cpu-baseline > $O/t_$n.$k.json 2> $O/t_$n.$k.err || { echo "$n FAILED"; exit 1; }
+    BEDGPU_LIB=$L timeout -k 10 200 python3 bench.py --full --load-only --steps 6 --warmup 1 --no-verify --no-cpu-baseline > $O/t_$n.$k.json 2> $O/t_$n.$k.err || { echo "$n FAILED"; exit 1; }
     python3 -c "import json;d=json.load(open('$O/t_$n.$k.json'));r=d['roofline'];print('%-10s avg %.4f ms step %.3f'%('$n',r['avg_ms'],d['ms_per_step']))"
   done
   BEDGPU_LIB=$L timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/f_$n -- python3 bench.py --load-only --steps 1 --warmup 1 --no-verify --no-cpu-baseline > $O/f_$n.json 2> $O/f_$n.err || exit 1

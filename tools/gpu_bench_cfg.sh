@@ -7,7 +7,7 @@ W=${WORKLOAD:-bedmap}
 O=gpurun_out/${ROUND:-r05}_cfg_$W
 mkdir -p $O
 df -h /tmp > $O/df.txt 2>&1; nproc >> $O/df.txt
-timeout -k 10 ${BENCH_T:-1000} python3 bench.py --workload $W --steps ${STEPS:-5} --warmup 1 --cpu-single-runs 0 \
+timeout -k 10 ${BENCH_T:-1000} python3 bench.py --full --workload $W --steps ${STEPS:-5} --warmup 1 --cpu-single-runs 0 \
   --cpu-fanout-runs ${FAN_RUNS:-3} ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/bench.json')); print(d['ms_per_step'], d['parity'], d.get('e2e_intervals_per_s'), d.get('gpu_vs_cpu'), (d.get('e2e') or {}).get('matches_reference'))"
 if [ -n "$PROF" ]; then

@@ -8,7 +8,7 @@ for r in $(seq 1 ${REPS:-2}); do
     for pf in plain prof; do
       A=""; [ $pf = prof ] && A="--profile-all"
       E="$ENVA"; [ $v = b ] && E="$ENVB"
-      env $E BG_NOOP=1 timeout -k 10 300 python3 bench.py --workload ${W:-intersect} --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-e2e $A > $O/b_${v}_${pf}_$r.json 2> $O/b_${v}_${pf}_$r.err || { tail -5 $O/b_${v}_${pf}_$r.err; exit 1; }
+      env $E BG_NOOP=1 timeout -k 10 300 python3 bench.py --full --workload ${W:-intersect} --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-e2e $A > $O/b_${v}_${pf}_$r.json 2> $O/b_${v}_${pf}_$r.err || { tail -5 $O/b_${v}_${pf}_$r.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/b_${v}_${pf}_$r.json')); print('$v $pf', d['ms_per_step'], d['parity'] and d['parity'].get('matches_reference'), d['roofline']['avg_ms'], d['roofline']['frac']); k=d.get('kernels_ms_per_step'); print(' ', {a: b for a, b in list(k.items())[:12]}) if k else None"
     done
   done

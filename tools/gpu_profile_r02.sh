@@ -13,5 +13,6 @@ for w in ${WORKLOADS:-intersect element-of bedmap bedmap-decimal closest}; do
   python3 tools/pmc_traffic.py gpurun_out/${T}_${w}_fetch gpurun_out/${T}_${w}_write gpurun_out/pmc_traffic_${w}.json || exit 1
   echo "$w profiled"
 done
-[ -n "$NO_BENCH" ] || timeout -k 10 600 python3 bench.py --steps 10 --warmup 2 > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || exit 1
+BO=${OUT_DIR:-bench_out}; mkdir -p $BO
+[ -n "$NO_BENCH" ] || timeout -k 10 600 python3 bench.py --full --steps 10 --warmup 2 > $BO/${T}_bench.json 2> $BO/${T}_bench.err || exit 1
 echo ALLDONE

@@ -15,6 +15,7 @@ for w in ${WORKLOADS:-intersect}; do
   fi
   echo "$w profiled"
 done
-[ -n "$NO_BENCH" ] || timeout -k 10 700 python3 bench.py --steps 10 --warmup 2 > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || exit 1
-cat gpurun_out/${T}_bench.json
+BO=${OUT_DIR:-bench_out}; mkdir -p $BO
+[ -n "$NO_BENCH" ] || timeout -k 10 700 python3 bench.py --full --steps 10 --warmup 2 > $BO/${T}_bench.json 2> $BO/${T}_bench.err || exit 1
+cat $BO/${T}_bench.json
 echo ALLDONE

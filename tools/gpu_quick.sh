@@ -8,6 +8,6 @@ if [ -n "$TESTS" ]; then
 fi
 for v in plain prof; do
   A=""; [ $v = prof ] && A="--profile-all"
-  timeout -k 10 300 python3 bench.py --workload ${W:-intersect} --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-e2e $A > $O/bench_$v.json 2> $O/bench_$v.err || { tail -5 $O/bench_$v.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --workload ${W:-intersect} --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-e2e $A > $O/bench_$v.json 2> $O/bench_$v.err || { tail -5 $O/bench_$v.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); print('$v', d['ms_per_step'], d['parity'] and d['parity'].get('matches_reference'), d['roofline']['kernel'], d['roofline']['avg_ms'], d['roofline']['frac']); print({k: v for k, v in list((d.get('kernels_ms_per_step') or {}).items())[:14]})"
 done
