@@ -58,6 +58,10 @@ int bg_hip_fail(bg_ctx* c, hipError_t e, const char* what) {
 
 void* bg_alloc(bg_ctx* c, size_t bytes) {
   bg_bind(c);  // the calling thread may drive several devices (bg_group)
+  if (c->fail_alloc && --c->fail_alloc == 0) {  // bg_fail_alloc_after
+    bg_fail(c, BG_E_NOMEM, "device allocation of " + std::to_string(bytes) + " bytes failed (injected)");
+    return nullptr;
+  }
   bytes = (bytes + 255) & ~(size_t)255;
   if (bytes == 0) bytes = 256;
   // best fit among cached blocks no larger than 2x the request
@@ -317,6 +321,22 @@ extern "C" int bg_stats(const bg_ctx* cc, char* buf, uint64_t cap) {
     s += line;
   }
   snprintf(buf, cap, "%s", s.c_str());
+  return 0;
+}
+
+extern "C" int bg_live(const bg_ctx* c, uint64_t* blocks, uint64_t* bytes) {
+  if (!c || !blocks || !bytes) return BG_E_ARG;
+  if (!c->deferred.empty())
+    return bg_fail(const_cast<bg_ctx*>(c), BG_E_HIP, "bg_live: releases still deferred to the side stream's join");
+  *blocks = c->live.size();
+  *bytes = 0;
+  for (const auto& b : c->live) *bytes += b.second;
+  return 0;
+}
+
+extern "C" int bg_fail_alloc_after(bg_ctx* c, uint64_t n) {
+  if (!c) return BG_E_ARG;
+  c->fail_alloc = n;
   return 0;
 }
 

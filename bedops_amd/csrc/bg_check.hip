@@ -118,17 +118,17 @@ extern "C" int bg_check(bg_ctx* c, const bg_input* in, int nfields, int has_rest
   const uint64_t nb = in->nbytes;
   if (nb == 0) return 0;
   const char* t = (const char*)in->data;
-  char* dt = nullptr;
+  BgHold hold(c);
   if (!in->on_device) {
-    dt = (char*)bg_alloc(c, nb);
-    if (!dt) return BG_E_NOMEM;
+    char* dt = hold.alloc<char>(nb);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_HIP(c, hipMemcpyAsync(dt, in->data, nb, hipMemcpyHostToDevice, c->stream));
     t = dt;
   }
   const uint64_t nt = (nb + CK_TILE - 1) / CK_TILE;
-  uint64_t* base = (uint64_t*)bg_alloc(c, 8 * nt);
-  uint64_t* w = (uint64_t*)bg_alloc(c, 8 * 8);  // first_data, key, range[4]
-  if (!base || !w) return BG_E_NOMEM;
+  uint64_t* base = hold.alloc<uint64_t>(nt);
+  uint64_t* w = hold.alloc<uint64_t>(8);  // first_data, key, range[4]
+  if (!hold.ok()) return BG_E_NOMEM;
   CkArgs A;
   A.t = t;
   A.nb = nb;
@@ -164,9 +164,6 @@ extern "C" int bg_check(bg_ctx* c, const bg_input* in, int nfields, int has_rest
     out->prev_off = r[2];
     out->prev_len = r[3] - r[2];
   }
-  bg_release(c, base);
-  bg_release(c, w);
-  if (dt) bg_release(c, dt);
   bg_mark(c, "check");
   return 0;
 }

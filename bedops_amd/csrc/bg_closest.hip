@@ -481,16 +481,16 @@ __global__ void __launch_bounds__(BG_NT) k_closest_serial(ClArgs A) {
 static int closest_pass(bg_ctx* c, ClArgs& A, bool* ovf) {
   *ovf = false;
   const uint64_t slots = 2ull * A.nchunks;
-  A.st_fp = (uint64_t*)bg_alloc(c, 8 * slots);
-  A.st_n = (uint32_t*)bg_alloc(c, 4 * slots);
-  A.st_c = (uint32_t*)bg_alloc(c, 4ull * A.cap * slots);
-  A.kl = (uint32_t*)bg_alloc(c, 4ull * A.cap * A.nchunks);
-  A.flag = (uint32_t*)bg_alloc(c, 4ull * A.nchunks);
-  A.nflag = (uint32_t*)bg_alloc(c, 8);
+  BgHold hold(c);
+  A.st_fp = hold.alloc<uint64_t>(slots);
+  A.st_n = hold.alloc<uint32_t>(slots);
+  A.st_c = hold.alloc<uint32_t>((uint64_t)A.cap * slots);
+  A.kl = hold.alloc<uint32_t>((uint64_t)A.cap * A.nchunks);
+  A.flag = hold.alloc<uint32_t>(A.nchunks);
+  A.nflag = hold.alloc<uint32_t>(2);
+  if (!hold.ok()) return BG_E_NOMEM;
   A.overflow = A.nflag + 1;
-  int rc = 0;
-  if (!A.st_fp || !A.st_n || !A.st_c || !A.kl || !A.flag || !A.nflag) rc = BG_E_NOMEM;
-  if (!rc) rc = bg_hip_ok(c, hipMemsetAsync(A.nflag, 0, 8, c->stream));
+  int rc = bg_hip_ok(c, hipMemsetAsync(A.nflag, 0, 8, c->stream));
   if (!rc) {
     BG_LAUNCH(c, "k_closest_chunks", k_closest_chunks, dim3(bg_blocks(A.nchunks, BG_NT)),
               dim3(BG_NT), A);
@@ -515,12 +515,6 @@ static int closest_pass(bg_ctx* c, ClArgs& A, bool* ovf) {
     rc = bg_hip_ok(c, hipGetLastError());
   }
   *ovf = h[1] != 0;
-  bg_release(c, A.st_fp);
-  bg_release(c, A.st_n);
-  bg_release(c, A.st_c);
-  bg_release(c, A.kl);
-  bg_release(c, A.flag);
-  bg_release(c, A.nflag);
   return rc;
 }
 
@@ -542,6 +536,8 @@ extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_c
   if (C->n >= (1ull << 32))
     return bg_fail(c, BG_E_UNSUPPORTED, "more than 2^32 rows in <query-file>");
   bg_result* r = new bg_result();
+  BgHold hold(c);
+  hold.own(r);
   r->ctx = c;
   r->set = set;
   r->kind = RES_CLOSEST;
@@ -551,10 +547,9 @@ extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_c
   r->copts.delim[15] = 0;
   r->n = Q->n;
   const uint64_t n = Q->n ? Q->n : 1;
-  r->left = (int64_t*)bg_alloc(c, 8 * n);
-  r->right = (int64_t*)bg_alloc(c, 8 * n);
-  if (!r->left || !r->right) { bg_result_free(r); return BG_E_NOMEM; }
-  if (Q->n == 0) { *out = r; return 0; }
+  r->left = hold.raw<int64_t>(n);
+  r->right = hold.raw<int64_t>(n);
+  if (!hold.ok()) return BG_E_NOMEM;
 
   ClArgs A;
   memset(&A, 0, sizeof(A));
@@ -569,7 +564,7 @@ extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_c
   int rc = 0;
   // the reader cache of the reference can hold many rows on nested inputs: grow the
   // per-chunk state capacity until it fits (bounded by device memory)
-  for (A.cap = CAP0;; A.cap *= 4) {
+  for (A.cap = CAP0; Q->n; A.cap *= 4) {
     bool ovf = false;
     rc = closest_pass(c, A, &ovf);
     if (rc || !ovf) break;
@@ -578,7 +573,8 @@ extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_c
       break;
     }
   }
-  if (rc) { bg_result_free(r); return rc; }
+  if (rc) return rc;
   *out = r;
+  r = nullptr;  // the caller's from here
   return 0;
 }

@@ -219,12 +219,14 @@ int bg_faster_windows(bg_ctx* c, const bg_table* R, const bg_table* M, int crit,
   A.cq = FS_CQ;
   A.cw = FS_CW;
   A.nchunks = (uint32_t)((nr + A.cq - 1) / A.cq);
-  A.s0 = (uint64_t*)bg_alloc(c, 8ull * A.nchunks);
-  A.s1 = (uint64_t*)bg_alloc(c, 8ull * A.nchunks);
-  A.flag = (uint32_t*)bg_alloc(c, 4ull * A.nchunks + 16);
+  BgHold hold(c);
+  A.s0 = hold.alloc<uint64_t>(A.nchunks);
+  A.s1 = hold.alloc<uint64_t>(A.nchunks);
+  A.flag = hold.alloc<uint32_t>(A.nchunks + 4);
+  if (!hold.ok()) return BG_E_NOMEM;
   A.nflag = A.flag + ((A.nchunks + 1) & ~1u);  // 8-byte aligned
-  int rc = (!A.s0 || !A.s1 || !A.flag) ? BG_E_NOMEM : 0;
-  if (!rc) {  // phase 1: the read positions (whi)
+  int rc = 0;
+  {  // phase 1: the read positions (whi)
     A.out = whi;
     rc = single ? fs_chain<1, true>(c, A) : fs_chain<1, false>(c, A);
   }
@@ -239,8 +241,5 @@ int bg_faster_windows(bg_ctx* c, const bg_table* R, const bg_table* M, int crit,
     A.out = wlo;
     rc = single ? fs_chain<3, true>(c, A) : fs_chain<3, false>(c, A);
   }
-  bg_release(c, A.s0);
-  bg_release(c, A.s1);
-  bg_release(c, A.flag);
   return rc;
 }

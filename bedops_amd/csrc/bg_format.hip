@@ -1471,6 +1471,7 @@ extern "C" int bg_result_format(bg_ctx* c, bg_result* r, uint64_t* nbytes) {
   FmtArgs A;
   fill_args(r, A);
   A.stop_row = ~0ULL;
+  BgHold hold(c);  // the text and the tile offsets move to r once they are complete
   if (r->kind == RES_IVL && r->nseg) {  // segmented: sizes known, one pass
     // every piece prints at most name + 3 + two 13-digit coordinates (< 2^40): with that
     // bound allocated up front, the counts come back with the kernel's completion (one host
@@ -1488,11 +1489,11 @@ extern "C" int bg_result_format(bg_ctx* c, bg_result* r, uint64_t* nbytes) {
       r->n_pending = false;
     }
     const unsigned nt = bg_blocks(ahead ? r->seg_nz : r->n, FT_TILE);
-    uint64_t* tb = (uint64_t*)bg_alloc(c, 8ull * (nt ? nt : 1));
-    r->text = (char*)bg_alloc(c, (ahead ? bound : tots[1]) + 16);
-    if (!tb || !r->text) return BG_E_NOMEM;
+    uint64_t* tb = hold.alloc<uint64_t>(nt ? nt : 1);
+    char* text = hold.alloc<char>((ahead ? bound : tots[1]) + 16);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_LAUNCH(c, "k_fmt_write", k_fmt_ivl_seg, dim3((unsigned)r->nseg), dim3(BG_NT), A, r->seg_off, r->seg_boff,
-              r->text, tb);
+              text, tb);
     BG_HIP(c, hipGetLastError());
     if (ahead) {
       BG_HIP(c, hipMemcpyAsync(&tots[0], r->seg_off + r->nseg, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1503,7 +1504,8 @@ extern "C" int bg_result_format(bg_ctx* c, bg_result* r, uint64_t* nbytes) {
     }
     (void)rc;
     const uint64_t total = tots[1];
-    r->toff = tb;
+    r->text = hold.give(text);
+    r->toff = hold.give(tb);
     r->nbytes = total;
     r->formatted = true;
     if (nbytes) *nbytes = total;
@@ -1512,15 +1514,14 @@ extern "C" int bg_result_format(bg_ctx* c, bg_result* r, uint64_t* nbytes) {
   }
   const unsigned nb = bg_blocks(r->n, FT_TILE);
   const unsigned nbc = bg_blocks(nb, FC_TILES);
-  uint64_t* tb = (uint64_t*)bg_alloc(c, 8ull * (nb ? nb : 1));
-  uint64_t* d_tot = (uint64_t*)bg_alloc(c, 8);
-  if (!tb || !d_tot) return BG_E_NOMEM;
+  uint64_t* tb = hold.alloc<uint64_t>(nb ? nb : 1);
+  uint64_t* d_tot = hold.alloc<uint64_t>(1);
+  // the count pass's row lengths, kept for the write pass
+  if ((A.kind == RES_MAP || A.kind == RES_CLOSEST) && r->n) A.rowlen = hold.alloc<uint32_t>(r->n);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemsetAsync(&c->dstat->first_bad, 0xff, 8, c->stream));
   BG_HIP(c, hipMemsetAsync(&c->dstat->stop_row, 0xff, 8, c->stream));
   static_assert(FT_TILE == BG_FMT_TILE, "format tile");
-  if ((A.kind == RES_MAP || A.kind == RES_CLOSEST) && r->n) {
-    A.rowlen = (uint32_t*)bg_alloc(c, 4 * r->n);  // (null: the write pass measures again)
-  }
   bool simple = A.kind == RES_MAP && !A.sci && !A.has_elem;
   for (int k = 0; simple && k < A.nops; ++k) simple = map_simple_op_host(A.ops[k]);
 count_again:
@@ -1552,16 +1553,16 @@ count_again:
   }
   if (c->hstat->first_bad != ~0ULL)
     return bg_fail(c, BG_E_UNSUPPORTED, "a value is outside the GPU formatter's range");
-  r->text = (char*)bg_alloc(c, total + 16);
-  if (!r->text) return BG_E_NOMEM;
+  char* text = hold.alloc<char>(total + 16);
+  if (!hold.ok()) return BG_E_NOMEM;
   A.st = c->dstat;
   A.total = total;
   if (A.rowlen) BG_HIP(c, hipMemsetAsync(&c->dstat->flags, 0, 8, c->stream));
   uint64_t* d_stop = nullptr;
   if (c->hstat->stop_row != ~0ULL) {  // the text ends inside this row (k_fmt_write finds where)
     A.stop_row = c->hstat->stop_row;
-    d_stop = (uint64_t*)bg_alloc(c, 8);
-    if (!d_stop) return BG_E_NOMEM;
+    d_stop = hold.alloc<uint64_t>(1);
+    if (!hold.ok()) return BG_E_NOMEM;
     A.stop_out = d_stop;
   }
   static const bool rows_fast = [] {  // BEDGPU_FMT_ROWS=0: k_fmt_write<RES_ROWS> (A/B)
@@ -1570,17 +1571,17 @@ count_again:
   }();
   if (nb) {
     switch (A.kind) {
-      case RES_IVL: BG_LAUNCH(c, "k_fmt_write", k_fmt_ivl_write, dim3(nb), dim3(BG_NT), A, tb, r->text); break;
+      case RES_IVL: BG_LAUNCH(c, "k_fmt_write", k_fmt_ivl_write, dim3(nb), dim3(BG_NT), A, tb, text); break;
       case RES_ROWS:
-        if (rows_fast) BG_LAUNCH(c, "k_fmt_write", k_fmt_rows_write, dim3(nb), dim3(BG_NT), A, tb, r->text);
-        else BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_ROWS>, dim3(nb), dim3(BG_NT), A, tb, r->text);
+        if (rows_fast) BG_LAUNCH(c, "k_fmt_write", k_fmt_rows_write, dim3(nb), dim3(BG_NT), A, tb, text);
+        else BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_ROWS>, dim3(nb), dim3(BG_NT), A, tb, text);
         break;
       case RES_MAP:
-        if (simple) BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_MAPS>, dim3(nb), dim3(BG_NT), A, tb, r->text);
-        else BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_MAP>, dim3(nb), dim3(BG_NT), A, tb, r->text);
+        if (simple) BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_MAPS>, dim3(nb), dim3(BG_NT), A, tb, text);
+        else BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_MAP>, dim3(nb), dim3(BG_NT), A, tb, text);
         break;
-      case RES_MULTI: BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_MULTI>, dim3(nb), dim3(BG_NT), A, tb, r->text); break;
-      default: BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_CLOSEST>, dim3(nb), dim3(BG_NT), A, tb, r->text);
+      case RES_MULTI: BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_MULTI>, dim3(nb), dim3(BG_NT), A, tb, text); break;
+      default: BG_LAUNCH(c, "k_fmt_write", k_fmt_write<RES_CLOSEST>, dim3(nb), dim3(BG_NT), A, tb, text);
     }
     BG_HIP(c, hipGetLastError());
     if (A.rowlen) {  // rows placed by the count pass's lengths must render to exactly those
@@ -1590,15 +1591,12 @@ count_again:
         return bg_fail(c, BG_E_INTERNAL, "formatter: a row rendered to another length than counted (its inputs changed between the passes)");
     }
   }
-  r->toff = tb;
-  bg_release(c, d_tot);
-  bg_release(c, A.rowlen);  // (stream-ordered: reused only by later work on c's stream)
   if (d_stop) {
-    rc = bg_fetch_u64(c, d_stop, &total);
-    bg_release(c, d_stop);
-    if (rc) return rc;
+    if ((rc = bg_fetch_u64(c, d_stop, &total))) return rc;
     r->stopped = true;
   }
+  r->text = hold.give(text);
+  r->toff = hold.give(tb);
   r->nbytes = total;
   r->formatted = true;
   if (nbytes) *nbytes = total;
@@ -1639,8 +1637,9 @@ extern "C" int bg_result_chrom_spans(bg_ctx* c, bg_result* r, uint64_t* offsets,
   if ((rc = bg_result_compact(c, r))) return rc;  // the row search reads contiguous pieces
   FmtArgs A;
   fill_args(r, A);
-  uint64_t* d = (uint64_t*)bg_alloc(c, 8ull * (nc + 1));
-  if (!d) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint64_t* d = hold.alloc<uint64_t>(nc + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
 #define BG_SPANS(K) BG_LAUNCH(c, "k_chrom_spans", k_chrom_spans<K>, dim3(bg_blocks(nc + 1, 64)), dim3(64), A, r->toff, nc, r->nbytes, d)
   switch (A.kind) {
     case RES_IVL: BG_SPANS(RES_IVL); break;
@@ -1653,7 +1652,6 @@ extern "C" int bg_result_chrom_spans(bg_ctx* c, bg_result* r, uint64_t* offsets,
   BG_HIP(c, hipGetLastError());
   BG_HIP(c, hipMemcpyAsync(offsets, d, 8ull * (nc + 1), hipMemcpyDeviceToHost, c->stream));
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  bg_release(c, d);
   return 0;
 }
 

@@ -305,10 +305,11 @@ extern "C" int bg_group_gather(bg_group* g, int nchrom, const char* const* text,
   }
   const bool root = g->rank0 == 0;
   char* dst = nullptr;
+  BgHold hold(c0);
   if (root) {
     bg_bind(c0);
-    dst = (char*)bg_alloc(c0, total ? total : 1);
-    if (!dst) return BG_E_NOMEM;
+    dst = hold.alloc<char>(total ? total : 1);
+    if (!hold.ok()) return BG_E_NOMEM;
   }
   // device copies (member 0's own runs, and every run when there are no communicators)
   for (const Run& r : runs) {
@@ -351,7 +352,6 @@ extern "C" int bg_group_gather(bg_group* g, int nchrom, const char* const* text,
           bg_bind(g->ctx[k]);
           hipStreamSynchronize(g->ctx[k]->stream);
         }
-        if (dst) bg_release(c0, dst);
         return rc;
       }
     }
@@ -361,7 +361,7 @@ extern "C" int bg_group_gather(bg_group* g, int nchrom, const char* const* text,
     BG_HIP(g->ctx[k], hipStreamSynchronize(g->ctx[k]->stream));
   }
   if (root) {
-    *out = dst;
+    *out = hold.give(dst);
     *out_len = total;
   }
   return 0;

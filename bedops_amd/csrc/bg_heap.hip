@@ -135,9 +135,9 @@ int bg_frest_gather(bg_ctx* c, const bg_table* M, int fields, const std::vector<
   txt.clear();
   if (!nr) return 0;
   BgHold hold(c);
-  uint64_t* drows = hold((uint64_t*)bg_alloc(c, 8 * nr));
-  uint64_t* dlen = hold((uint64_t*)bg_alloc(c, 8 * (nr + 1)));
-  if (!drows || !dlen) return BG_E_NOMEM;
+  uint64_t* drows = hold.alloc<uint64_t>(nr);
+  uint64_t* dlen = hold.alloc<uint64_t>(nr + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemcpyAsync(drows, rows.data(), 8 * nr, hipMemcpyHostToDevice, c->stream));
   BG_LAUNCH(c, "k_heap_rest_len", k_heap_rest_len, dim3(bg_blocks(nr, BG_NT)), dim3(BG_NT), drows, nr, M->text,
             M->rest_off, M->rest_len, fields, dlen);
@@ -145,8 +145,8 @@ int bg_frest_gather(bg_ctx* c, const bg_table* M, int fields, const std::vector<
   BG_HIP(c, hipMemcpyAsync(len.data(), dlen, 8 * nr, hipMemcpyDeviceToHost, c->stream));
   BG_HIP(c, hipStreamSynchronize(c->stream));
   for (uint64_t i = 0; i < nr; ++i) off[i + 1] = off[i] + len[i];
-  char* dtxt = hold((char*)bg_alloc(c, off[nr] + 1));
-  if (!dtxt) return BG_E_NOMEM;
+  char* dtxt = hold.alloc<char>(off[nr] + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemcpyAsync(dlen, off.data(), 8 * nr, hipMemcpyHostToDevice, c->stream));
   BG_LAUNCH(c, "k_heap_rest_copy", k_heap_rest_copy, dim3(bg_blocks(nr, BG_NT)), dim3(BG_NT), drows, nr, M->text,
             M->rest_off, M->rest_len, fields, dlen, dtxt);
@@ -220,10 +220,11 @@ int bg_heap_addr(bg_ctx* c, bg_set* set, const bg_table* R, const bg_table* M, i
   uint32_t* dli = nullptr;
   uint32_t* dlr = nullptr;
   uint32_t* drk = nullptr;
+  BgHold hold(c);
   if (nm && M->rest_off) {
-    dli = (uint32_t*)bg_alloc(c, 4 * nm);
-    dlr = (uint32_t*)bg_alloc(c, 4 * nm);
-    if (!dli || !dlr) return BG_E_NOMEM;
+    dli = hold.alloc<uint32_t>(nm);
+    dlr = hold.alloc<uint32_t>(nm);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_LAUNCH(c, "k_heap_lens", k_heap_lens, dim3(bg_blocks(nm, BG_NT)), dim3(BG_NT), M->text, M->rest_off,
               M->rest_len, nm, fields, dli, dlr);
     BG_HIP(c, hipGetLastError());
@@ -234,13 +235,14 @@ int bg_heap_addr(bg_ctx* c, bg_set* set, const bg_table* R, const bg_table* M, i
   uint64_t nrun = 0;
   std::vector<uint64_t> longs;
   if (nm && M->rest_off && !spec->faster) {
-    drk = (uint32_t*)bg_alloc(c, 4 * nm);
-    uint8_t* f = (uint8_t*)bg_alloc(c, nm);
-    uint64_t* dl = (uint64_t*)bg_alloc(c, 8 * (nm + 1));  // long runs (count in the last slot)
-    if (!drk || !f || !dl) return BG_E_NOMEM;
+    drk = hold.alloc<uint32_t>(nm);
+    uint8_t* f = hold.alloc<uint8_t>(nm);
+    uint64_t* dl = hold.alloc<uint64_t>(nm + 1);  // long runs (count in the last slot)
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_LAUNCH(c, "k_heap_run_flags", k_heap_run_flags, dim3(bg_blocks(nm, BG_NT)), dim3(BG_NT), M->ks, M->ke, nm, f);
     int rc = bg_compact_flags(c, f, nm, &run0, &nrun);
     if (rc) return rc;
+    hold(run0);
     BG_HIP(c, hipMemsetAsync(dl + nm, 0, 8, c->stream));
     BG_LAUNCH(c, "k_heap_rest_rank", k_heap_rest_rank, dim3(bg_blocks(nm, BG_NT)), dim3(BG_NT), run0, nrun, nm,
               M->text, M->rest_off, M->rest_len, fields, drk, dl, (unsigned long long*)(dl + nm));
@@ -255,9 +257,7 @@ int bg_heap_addr(bg_ctx* c, bg_set* set, const bg_table* R, const bg_table* M, i
       std::sort(longs.begin(), longs.end());
       if ((rc = heap_long_ranks(c, M, fields, run0, nrun, longs, hrank))) return rc;
     }
-    bg_release(c, f);
-    bg_release(c, dl);
-    bg_release(c, run0);
+    hold.drop(f, dl, run0);
   }
   if (nr && !single) {
     BG_HIP(c, hipMemcpyAsync(hRS.data(), R->ks, 8 * nr, hipMemcpyDeviceToHost, c->stream));
@@ -269,9 +269,7 @@ int bg_heap_addr(bg_ctx* c, bg_set* set, const bg_table* R, const bg_table* M, i
     BG_HIP(c, hipMemcpyAsync(hME.data(), M->ke, 8 * nm, hipMemcpyDeviceToHost, c->stream));
   }
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  bg_release(c, dli);
-  bg_release(c, dlr);
-  bg_release(c, drk);
+  hold.drop(dli, dlr, drk);
   auto name_len = [&](int64_t key) -> uint32_t {
     const uint64_t g = (uint64_t)(key >> BG_KEY_SHIFT);
     return g < set->names.size() ? (uint32_t)set->names[g].size() : 0;
@@ -314,14 +312,14 @@ int bg_heap_addr(bg_ctx* c, bg_set* set, const bg_table* R, const bg_table* M, i
                 [&](uint32_t a, uint32_t b) { return addr[a] < addr[b]; });
     m = t;
   }
-  int64_t* d = (int64_t*)bg_alloc(c, 8 * (nm ? nm : 1) + 4 * nm);
-  if (!d) return BG_E_NOMEM;
+  int64_t* d = (int64_t*)hold.alloc<char>(8 * (nm ? nm : 1) + 4 * nm);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (nm) {
     BG_HIP(c, hipMemcpyAsync(d, addr.data(), 8 * nm, hipMemcpyHostToDevice, c->stream));
     BG_HIP(c, hipMemcpyAsync(d + nm, ord.data(), 4 * nm, hipMemcpyHostToDevice, c->stream));
   }
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  *out = d;
+  *out = hold.give(d);
   return 0;
 }
 
@@ -329,8 +327,9 @@ int bg_heap_addr(bg_ctx* c, bg_set* set, const bg_table* R, const bg_table* M, i
 int bg_heap_ties(bg_ctx* c, const bg_table* M, int fields, bool rest, bool* any) {
   *any = false;
   if (M->n < 2) return 0;
-  unsigned int* d = (unsigned int*)bg_alloc(c, 4);
-  if (!d) return BG_E_NOMEM;
+  BgHold hold(c);
+  unsigned int* d = hold.alloc<unsigned int>(1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemsetAsync(d, 0, 4, c->stream));
   BG_LAUNCH(c, "k_heap_ties", k_heap_ties, dim3(bg_blocks(M->n - 1, BG_NT)), dim3(BG_NT), M->ks, M->ke, M->n,
             M->text, M->rest_off, M->rest_len, fields, rest ? 1 : 0, d);
@@ -338,7 +337,6 @@ int bg_heap_ties(bg_ctx* c, const bg_table* M, int fields, bool rest, bool* any)
   unsigned int h = 0;
   BG_HIP(c, hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, c->stream));
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  bg_release(c, d);
   *any = h != 0;
   return 0;
 }

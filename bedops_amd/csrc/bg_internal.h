@@ -113,6 +113,7 @@ struct bg_ctx {
   // contexts on different devices can be driven from different host threads)
   std::vector<bg_buf> free_list;
   std::unordered_map<void*, size_t> live;
+  uint64_t fail_alloc = 0;  // bg_fail_alloc_after: allocations until the injected failure (0: off)
   // stage timing
   bool stats = false;
   std::vector<std::pair<std::string, hipEvent_t>> marks;
@@ -251,20 +252,41 @@ void* bg_pin_take(bg_ctx* c, size_t bytes);
 // allocator / error helpers (bg_api.cpp)
 void* bg_alloc(bg_ctx* c, size_t bytes);
 void bg_release(bg_ctx* c, void* p);
-// device blocks released to the context's pool on every exit path of a host function
+// The one owner of a host function's device temporaries: what it holds goes back to the
+// context's pool on every exit path. Blocks are held by value (alloc / operator()), compound
+// objects (Ivl, Multi, Events, a half-built bg_result*, ...: anything with a bg_free) by
+// address, so whatever they hold when the function returns is freed; such an object lives in
+// the guard's block or outside it (a std::vector of them is declared before the guard).
+// Ownership leaves only by give() (blocks) or by emptying the object (bg_free and the
+// hand-offs to a result do). No block may reach a kernel or copy before ok() was checked.
 struct BgHold {
   bg_ctx* c;
+  bool bad = false;  // an allocation failed
   std::vector<void*> p;
+  std::vector<std::pair<void*, void (*)(bg_ctx*, void*)>> obj;
   explicit BgHold(bg_ctx* cc) : c(cc) {}
-  template <class T>
-  T* operator()(T* q) {
-    p.push_back((void*)q);
+  BgHold(const BgHold&) = delete;
+  template <class T> T* operator()(T* q) { p.push_back((void*)q); return q; }  // adopt
+  // n elements of T for a field of an own()ed object / held by the guard itself
+  template <class T> T* raw(size_t n) { T* q = (T*)bg_alloc(c, sizeof(T) * n); bad |= !q; return q; }
+  template <class T> T* alloc(size_t n) { return (*this)(raw<T>(n)); }
+  bool ok() const { return !bad; }
+  template <class T> T* give(T* q) {  // the caller of give() owns q from here
+    auto it = std::find(p.begin(), p.end(), (void*)q);
+    if (it != p.end()) p.erase(it);
     return q;
+  }
+  template <class... T> void drop(T*... q) { (bg_release(c, give(q)), ...); }  // early release (peak memory)
+  template <class... T> void own(T&... v) {
+    (obj.push_back({(void*)&v, [](bg_ctx* cc, void* o) { bg_free(cc, *(T*)o); }}), ...);
   }
   ~BgHold() {
     for (void* q : p) bg_release(c, q);
+    for (auto& o : obj) o.second(c, o.first);
   }
 };
+static inline void bg_free(bg_ctx*, bg_result*& r) { bg_result_free(r); r = nullptr; }
+static inline void bg_free(bg_ctx*, bg_set*& s) { bg_set_free(s); s = nullptr; }
 int bg_fail(bg_ctx* c, int code, const std::string& msg);
 int bg_hip_fail(bg_ctx* c, hipError_t e, const char* what);
 void bg_mark(bg_ctx* c, const char* name);
@@ -315,7 +337,12 @@ struct Ivl {
   uint64_t seg_nz = 0;
   bool n_pending = false;
 };
-void ivl_free(bg_ctx* c, Ivl& v);
+void ivl_free(bg_ctx* c, Ivl& v);  // a borrowed view (owned == false) is only forgotten
+static inline void bg_free(bg_ctx* c, Ivl& v) { ivl_free(c, v); }
+template <class T>
+static void bg_free(bg_ctx* c, std::vector<T>& v) {
+  for (T& x : v) bg_free(c, x);
+}
 int ivl_alloc(bg_ctx* c, Ivl& v, uint64_t n);
 Ivl bg_table_ivl(bg_table* T);
 // the components of one table: a view of a BG_BED3_SET table's set, computed otherwise
@@ -325,7 +352,8 @@ int bg_need_rows(bg_ctx* c, bg_set* set, const int* files, int nf, const char* w
 // components (maximal touching-merged pieces) of one start-sorted list / of a union
 int bg_components(bg_ctx* c, const Ivl& in, Ivl& out);
 int bg_union_components(bg_ctx* c, bg_set* set, const int* files, int nf, Ivl& out);
-bg_result* bg_new_ivl_result(bg_ctx* c, bg_set* set, Ivl& v);
+// v's blocks move to a new RES_IVL result (a borrowed v is copied); *out is written on success
+int bg_new_ivl_result(bg_ctx* c, bg_set* set, Ivl& v, bg_result** out);
 int bg_check_files(bg_ctx* c, bg_set* set, const int* files, int nf, int minf);
 int bg_compact_flags(bg_ctx* c, const uint8_t* flag, uint64_t n, uint64_t** rows, uint64_t* total);
 // full_rest() of each listed map row copied to the host: row i's bytes are txt[off[i], off[i+1])
@@ -342,9 +370,10 @@ int bg_sort_u64(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n);
 // count pass -> scan -> allocate exact output -> write pass
 template <typename CountFn, typename WriteFn>
 static int count_scan_write(bg_ctx* c, unsigned nb, CountFn cf, WriteFn wf, uint64_t* total) {
-  uint64_t* cnt = (uint64_t*)bg_alloc(c, 8ull * (nb ? nb : 1));
-  uint64_t* d_tot = (uint64_t*)bg_alloc(c, 8);
-  if (!cnt || !d_tot) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint64_t* cnt = hold.alloc<uint64_t>(nb ? nb : 1);
+  uint64_t* d_tot = hold.alloc<uint64_t>(1);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (nb) {
     cf(cnt);
     BG_HIP(c, hipGetLastError());
@@ -352,10 +381,9 @@ static int count_scan_write(bg_ctx* c, unsigned nb, CountFn cf, WriteFn wf, uint
   int rc = bg_scan_sum_u64(c, cnt, cnt, nb, d_tot);
   if (rc) return rc;
   if ((rc = bg_fetch_u64(c, d_tot, total))) return rc;
-  bg_release(c, d_tot);
+  hold.drop(d_tot);
   if ((rc = wf(cnt, *total))) return rc;
   BG_HIP(c, hipGetLastError());
-  bg_release(c, cnt);
   return 0;
 }
 

@@ -2972,6 +2972,11 @@ extern "C" int bg_load(bg_ctx* c, int n, const bg_input* inputs, bg_set** out) {
       T->ks = (int64_t*)bg_alloc(c, 8);
       T->ke = (int64_t*)bg_alloc(c, 8);
     }
+  for (bg_table* T : s->t)
+    if (T->is_set ? (!T->cs || !T->ce) : (!T->ks || !T->ke)) {
+      bg_set_free(s);
+      return BG_E_NOMEM;
+    }
   bg_mark(c, "parse");
   *out = s;
   return 0;

@@ -334,22 +334,19 @@ __global__ void k_mz_single(const uint64_t* __restrict__ f, const uint64_t* __re
 static int map_zero_prep_single(bg_ctx* c, const bg_table* R, bg_result* res) {
   const uint64_t n = R->n;
   if (!n) return 0;
-  res->zin = (int64_t*)bg_alloc(c, 8 * n);
-  res->zout = (int64_t*)bg_alloc(c, 8 * n);
-  uint64_t* f = (uint64_t*)bg_alloc(c, 8 * n);
-  uint64_t* p = (uint64_t*)bg_alloc(c, 8 * n);
-  int64_t* j0 = (int64_t*)bg_alloc(c, 8 * n);
-  int64_t* j1 = (int64_t*)bg_alloc(c, 8 * n);
-  int rc = (!res->zin || !res->zout || !f || !p || !j0 || !j1) ? BG_E_NOMEM : 0;
-  if (!rc) rc = bg_faster_windows(c, R, R, BG_OVR_BP, 0, 0, 1.0, true, f, p, j0, j1);
+  BgHold hold(c);
+  res->zin = hold.raw<int64_t>(n);
+  res->zout = hold.raw<int64_t>(n);
+  uint64_t* f = hold.alloc<uint64_t>(n);
+  uint64_t* p = hold.alloc<uint64_t>(n);
+  int64_t* j0 = hold.alloc<int64_t>(n);
+  int64_t* j1 = hold.alloc<int64_t>(n);
+  if (!hold.ok()) return BG_E_NOMEM;
+  int rc = bg_faster_windows(c, R, R, BG_OVR_BP, 0, 0, 1.0, true, f, p, j0, j1);
   if (!rc) {
     BG_LAUNCH(c, "k_mz_single", k_mz_single, dim3(bg_blocks(n, BG_NT)), dim3(BG_NT), f, p, n, res->zin, res->zout);
     rc = bg_hip_ok(c, hipGetLastError());
   }
-  bg_release(c, f);
-  bg_release(c, p);
-  bg_release(c, j0);
-  bg_release(c, j1);
   return rc;
 }
 
@@ -368,58 +365,53 @@ __global__ void k_mz_deque(const uint64_t* __restrict__ f, const uint64_t* __res
 static int map_deque_prep(bg_ctx* c, const bg_table* R, const bg_table* M, bg_result* res) {
   const uint64_t nr = R->n, nm = M->n;
   if (!nr || !nm) return 0;
-  res->zin = (int64_t*)bg_alloc(c, 8 * nm);
-  res->zout = (int64_t*)bg_alloc(c, 8 * nm);
-  uint64_t* f = (uint64_t*)bg_alloc(c, 8 * nr);
-  uint64_t* p = (uint64_t*)bg_alloc(c, 8 * nr);
-  int64_t* j0 = (int64_t*)bg_alloc(c, 8 * nm);
-  int64_t* j1 = (int64_t*)bg_alloc(c, 8 * nm);
-  int rc = (!res->zin || !res->zout || !f || !p || !j0 || !j1) ? BG_E_NOMEM : 0;
-  if (!rc) rc = bg_faster_windows(c, R, M, BG_OVR_BP, 0, 0, 1.0, false, f, p, j0, j1);
+  BgHold hold(c);
+  res->zin = hold.raw<int64_t>(nm);
+  res->zout = hold.raw<int64_t>(nm);
+  uint64_t* f = hold.alloc<uint64_t>(nr);
+  uint64_t* p = hold.alloc<uint64_t>(nr);
+  int64_t* j0 = hold.alloc<int64_t>(nm);
+  int64_t* j1 = hold.alloc<int64_t>(nm);
+  if (!hold.ok()) return BG_E_NOMEM;
+  int rc = bg_faster_windows(c, R, M, BG_OVR_BP, 0, 0, 1.0, false, f, p, j0, j1);
   if (!rc) {
     BG_LAUNCH(c, "k_mz_deque", k_mz_deque, dim3(bg_blocks(nm, BG_NT)), dim3(BG_NT), f, p, nr, j0, nm, res->zin,
               res->zout);
     rc = bg_hip_ok(c, hipGetLastError());
   }
-  bg_release(c, f);
-  bg_release(c, p);
-  bg_release(c, j0);
-  bg_release(c, j1);
   return rc;
 }
 
 static int map_zero_prep(bg_ctx* c, const bg_table* R, const bg_table* M, bg_result* res) {
   const uint64_t nr = R->n, nm = M->n;
   if (!nr || !nm) return 0;
-  res->zin = (int64_t*)bg_alloc(c, 8 * nm);
-  res->zout = (int64_t*)bg_alloc(c, 8 * nm);
-  int64_t* PM = (int64_t*)bg_alloc(c, 8 * nr);
-  int64_t* P = (int64_t*)bg_alloc(c, 8 * nr);
-  uint8_t* f = (uint8_t*)bg_alloc(c, max(nr, nm));
-  if (!res->zin || !res->zout || !PM || !P || !f) return BG_E_NOMEM;
+  BgHold hold(c);
+  res->zin = hold.raw<int64_t>(nm);
+  res->zout = hold.raw<int64_t>(nm);
+  int64_t* PM = hold.alloc<int64_t>(nr);
+  int64_t* P = hold.alloc<int64_t>(nr);
+  uint8_t* f = hold.alloc<uint8_t>(max(nr, nm));
+  if (!hold.ok()) return BG_E_NOMEM;
   int rc = bg_scan_max_i64(c, R->ke, PM, nr, LLONG_MIN);
   if (rc) return rc;
   uint64_t *seg = nullptr, *zm = nullptr, *zr = nullptr, nseg = 0, nz = 0, nzr = 0;
   BG_LAUNCH(c, "k_mz_flags", k_mz_flags, dim3(bg_blocks(nr, BG_NT)), dim3(BG_NT), R->ks, R->ke, PM, nr, f);
   if ((rc = bg_compact_flags(c, f, nr, &seg, &nseg))) return rc;
+  hold(seg);
   BG_LAUNCH(c, "k_mz_flags", k_mz_flags, dim3(bg_blocks(nm, BG_NT)), dim3(BG_NT), M->ks, M->ke,
             (const int64_t*)nullptr, nm, f);
   if ((rc = bg_compact_flags(c, f, nm, &zm, &nz))) return rc;
+  hold(zm);
   BG_LAUNCH(c, "k_mz_flags", k_mz_flags, dim3(bg_blocks(nr, BG_NT)), dim3(BG_NT), R->ks, R->ke,
             (const int64_t*)nullptr, nr, f);
   if ((rc = bg_compact_flags(c, f, nr, &zr, &nzr))) return rc;
+  hold(zr);
   if (nseg)
     BG_LAUNCH(c, "k_mz_walk", k_mz_walk, dim3(bg_blocks(nseg, BG_NT)), dim3(BG_NT), R->ks, R->ke, nr,
               M->ks, nm, zm, nz, seg, nseg, P);
   BG_LAUNCH(c, "k_mz_member", k_mz_member, dim3(bg_blocks(nm, BG_NT)), dim3(BG_NT), R->ks, R->ke, nr,
             M->ks, M->ke, nm, P, zr, nzr, res->zin, res->zout);
   BG_HIP(c, hipGetLastError());
-  bg_release(c, PM);
-  bg_release(c, P);
-  bg_release(c, f);
-  bg_release(c, seg);
-  bg_release(c, zm);
-  bg_release(c, zr);
   return 0;
 }
 
@@ -831,8 +823,8 @@ __global__ void k_mev_pick(const uint64_t* __restrict__ off, uint64_t nr, const 
 static int ev_order(bg_ctx* c, const EvArgs& E, const bg_table* M, int fields, uint32_t* ro) {
   const uint64_t nm = E.nm;
   BgHold hold(c);
-  uint64_t* dl = hold((uint64_t*)bg_alloc(c, 8 * (nm + 1)));
-  if (!dl) return BG_E_NOMEM;
+  uint64_t* dl = hold.alloc<uint64_t>(nm + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemsetAsync(dl + nm, 0, 8, c->stream));
   BG_LAUNCH(c, "k_ev_rank", k_ev_rank, dim3(bg_blocks(nm, BG_NT)), dim3(BG_NT), E, ro, dl,
             (unsigned long long*)(dl + nm));
@@ -889,8 +881,9 @@ template <int CRIT>
 static int map_running_sums_t(bg_ctx* c, const EvArgs& A, bool need_sq, bg_result* res) {
   const uint64_t nr = A.nr;
   const unsigned nb = bg_blocks(nr, BG_NT);
-  uint64_t* off = (uint64_t*)bg_alloc(c, 8 * (nr + 1));
-  if (!off) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint64_t* off = hold.alloc<uint64_t>(nr + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_mev_count", (k_mev<CRIT, false>), dim3(nb), dim3(BG_NT), A, off,
             (const uint64_t*)nullptr, (double*)nullptr, (double*)nullptr);
   BG_HIP(c, hipGetLastError());
@@ -898,21 +891,16 @@ static int map_running_sums_t(bg_ctx* c, const EvArgs& A, bool need_sq, bg_resul
   uint64_t E = 0;
   if (rc || (rc = bg_fetch_u64(c, off + nr, &E))) return rc;
   const uint64_t E1 = E ? E : 1;
-  double* X = (double*)bg_alloc(c, 8 * E1);
-  double* X2 = need_sq ? (double*)bg_alloc(c, 8 * E1) : nullptr;
-  double* SA = (double*)bg_alloc(c, 8 * E1);
-  double* QA = need_sq ? (double*)bg_alloc(c, 8 * E1) : nullptr;
-  if (!X || !SA || (need_sq && (!X2 || !QA))) return BG_E_NOMEM;
+  double* X = hold.alloc<double>(E1);
+  double* X2 = need_sq ? hold.alloc<double>(E1) : nullptr;
+  double* SA = hold.alloc<double>(E1);
+  double* QA = need_sq ? hold.alloc<double>(E1) : nullptr;
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_mev_write", (k_mev<CRIT, true>), dim3(nb), dim3(BG_NT), A, (uint64_t*)nullptr,
             (const uint64_t*)off, X, X2);
   if (E) BG_LAUNCH(c, "k_mev_chain", k_mev_chain, dim3(1), dim3(64), X, X2, E, SA, QA);
   BG_LAUNCH(c, "k_mev_pick", k_mev_pick, dim3(nb), dim3(BG_NT), off, nr, SA, QA, res->dsum, res->dsq);
   BG_HIP(c, hipGetLastError());
-  bg_release(c, off);
-  bg_release(c, X);
-  bg_release(c, X2);
-  bg_release(c, SA);
-  bg_release(c, QA);
   return 0;
 }
 
@@ -1130,17 +1118,18 @@ template <int CRIT>
 static int map_tmean_t(bg_ctx* c, const EvArgs& A, const int32_t* cnt, const bg_map_opts* o, bg_result* res) {
   const uint64_t nr = A.nr;
   const unsigned nb = bg_blocks(nr, BG_NT);
-  uint64_t* flag = (uint64_t*)bg_alloc(c, 8 * nr);
-  uint64_t* pos = (uint64_t*)bg_alloc(c, 8 * (nr + 1));
-  if (!flag || !pos) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint64_t* flag = hold.alloc<uint64_t>(nr);
+  uint64_t* pos = hold.alloc<uint64_t>(nr + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_tm_seg", k_tm_seg<CRIT>, dim3(nb), dim3(BG_NT), A, flag);
   BG_HIP(c, hipGetLastError());
   int rc = bg_scan_sum_u64(c, flag, pos, nr, pos + nr);
   uint64_t nseg = 0;
   if (rc || (rc = bg_fetch_u64(c, pos + nr, &nseg))) return rc;
-  uint64_t* seg = (uint64_t*)bg_alloc(c, 8 * (nseg ? nseg : 1));
-  uint64_t* soff = (uint64_t*)bg_alloc(c, 8 * (nseg + 1));
-  if (!seg || !soff) return BG_E_NOMEM;
+  uint64_t* seg = hold.alloc<uint64_t>(nseg ? nseg : 1);
+  uint64_t* soff = hold.alloc<uint64_t>(nseg + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_tm_list", k_tm_list, dim3(nb), dim3(BG_NT), flag, pos, nr, seg);
   const unsigned ns = bg_blocks(nseg ? nseg : 1, BG_NT);
   BG_LAUNCH(c, "k_tm_cap", k_tm_cap, dim3(ns), dim3(BG_NT), seg, nseg, nr, cnt, soff);
@@ -1148,9 +1137,9 @@ static int map_tmean_t(bg_ctx* c, const EvArgs& A, const int32_t* cnt, const bg_
   uint64_t slots = 0;
   if ((rc = bg_scan_sum_u64(c, soff, soff, nseg, soff + nseg)) || (rc = bg_fetch_u64(c, soff + nseg, &slots)))
     return rc;
-  double* SV = (double*)bg_alloc(c, 8 * (slots ? slots : 1));
-  uint64_t* SI = (uint64_t*)bg_alloc(c, 8 * (slots ? slots : 1));
-  if (!SV || !SI) return BG_E_NOMEM;
+  double* SV = hold.alloc<double>(slots ? slots : 1);
+  uint64_t* SI = hold.alloc<uint64_t>(slots ? slots : 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   for (int q = 0; q < o->n_ops && !rc; ++q) {
     if (o->ops[q] != BG_MAP_TMEAN) continue;
     TmArgs T;
@@ -1160,19 +1149,13 @@ static int map_tmean_t(bg_ctx* c, const EvArgs& A, const int32_t* cnt, const bg_
     T.doKth = fabs(1.0 - T.lo - T.hi) <= DBL_EPSILON;
     T.symmetric = fabs(T.lo - T.hi) <= DBL_EPSILON;
     T.lower = T.lo > 0 && !T.doKth;
-    res->tmv[q] = (double*)bg_alloc(c, 8 * nr);
-    if (!res->tmv[q]) return BG_E_NOMEM;
+    res->tmv[q] = hold.raw<double>(nr);
+    if (!hold.ok()) return BG_E_NOMEM;
     if (nseg) BG_LAUNCH(c, "k_tm_replay", k_tm_replay<CRIT>, dim3(ns), dim3(BG_NT), A, T, seg, nseg, soff, SV, SI,
                         res->tmv[q]);
     rc = bg_hip_ok(c, hipGetLastError());
   }
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  bg_release(c, flag);
-  bg_release(c, pos);
-  bg_release(c, seg);
-  bg_release(c, soff);
-  bg_release(c, SV);
-  bg_release(c, SI);
   return rc;
 }
 
@@ -1219,9 +1202,10 @@ __global__ void k_gather_i64(const int64_t* __restrict__ src, const uint64_t* __
 // each class), with their starts: res->lrows
 static int map_long_rows(bg_ctx* c, const bg_table* M, bg_result* res) {
   const uint64_t n = M->n;
-  uint8_t* cls = (uint8_t*)bg_alloc(c, n);
-  uint8_t* f = (uint8_t*)bg_alloc(c, n);
-  if (!cls || !f) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint8_t* cls = hold.alloc<uint8_t>(n);
+  uint8_t* f = hold.alloc<uint8_t>(n);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_len_class", k_len_class, dim3(bg_blocks(n, BG_NT)), dim3(BG_NT), M->ks, M->ke, n,
             (int64_t)BG_LONG_THR, cls);
   std::vector<uint64_t*> lists;
@@ -1234,27 +1218,25 @@ static int map_long_rows(bg_ctx* c, const bg_table* M, bg_result* res) {
     uint64_t cnt = 0;
     int rc = bg_compact_flags(c, f, n, &idx, &cnt);
     if (rc) return rc;
-    lists.push_back(idx);
+    lists.push_back(hold(idx));
     counts.push_back(cnt);
   }
   uint64_t tot = 0;
   std::vector<uint64_t> coff(lists.size() + 1, 0);
   for (size_t k = 0; k < lists.size(); ++k) coff[k + 1] = coff[k] + counts[k];
   tot = coff.back();
-  uint64_t* idx = (uint64_t*)bg_alloc(c, 8 * (tot ? tot : 1));
-  int64_t* ls = (int64_t*)bg_alloc(c, 8 * (tot ? tot : 1));
-  uint64_t* dco = (uint64_t*)bg_alloc(c, 8 * coff.size());
-  if (!idx || !ls || !dco) return BG_E_NOMEM;
+  uint64_t* idx = hold.alloc<uint64_t>(tot ? tot : 1);
+  int64_t* ls = hold.alloc<int64_t>(tot ? tot : 1);
+  uint64_t* dco = hold.alloc<uint64_t>(coff.size());
+  if (!hold.ok()) return BG_E_NOMEM;
   for (size_t k = 0; k < lists.size(); ++k) {
     if (counts[k]) BG_HIP(c, hipMemcpyAsync(idx + coff[k], lists[k], 8 * counts[k], hipMemcpyDeviceToDevice, c->stream));
-    bg_release(c, lists[k]);
+    hold.drop(lists[k]);
   }
   if (tot) BG_LAUNCH(c, "k_gather_i64", k_gather_i64, dim3(bg_blocks(tot, BG_NT)), dim3(BG_NT), M->ks, idx, tot, ls);
   BG_HIP(c, hipMemcpyAsync(dco, coff.data(), 8 * coff.size(), hipMemcpyHostToDevice, c->stream));
   BG_HIP(c, hipStreamSynchronize(c->stream));  // coff is a host vector
-  bg_release(c, cls);
-  bg_release(c, f);
-  res->lrows = LongRows{idx, ls, dco, (int)lists.size(), (int64_t)BG_LONG_THR};
+  res->lrows = LongRows{hold.give(idx), hold.give(ls), hold.give(dco), (int)lists.size(), (int64_t)BG_LONG_THR};
   return 0;
 }
 
@@ -1399,6 +1381,8 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
   BG_HIP(c, hipMemsetAsync(c->dstat, 0, sizeof(bg_dstatus), c->stream));
   const uint64_t n1 = R->n ? R->n : 1;
   bg_result* res = new bg_result();
+  BgHold hold(c);
+  hold.own(res);
   res->ctx = c;
   res->set = set;
   res->kind = RES_MAP;
@@ -1407,57 +1391,41 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
   if (!res->mopts.multidelim[0]) strcpy(res->mopts.multidelim, ";");  // unset: the default
   res->tab = ref;
   res->single = ref == map;
-  res->cnt = (int32_t*)bg_alloc(c, 4 * n1);
-  if (need & NEED_SUM) res->isum = (int64_t*)bg_alloc(c, 8 * n1);
+  res->cnt = hold.raw<int32_t>(n1);
+  if (need & NEED_SUM) res->isum = hold.raw<int64_t>(n1);
   if (need & NEED_EXT) {
-    res->vmin = (double*)bg_alloc(c, 8 * n1);
-    res->vmax = (double*)bg_alloc(c, 8 * n1);
+    res->vmin = hold.raw<double>(n1);
+    res->vmax = hold.raw<double>(n1);
   }
-  if (need & NEED_BASES) res->bases = (uint64_t*)bg_alloc(c, 8 * n1);
-  if (need & NEED_UNIQ) res->uniq = (uint32_t*)bg_alloc(c, 4 * n1);
-  if (need & NEED_SQ) res->isq = (int64_t*)bg_alloc(c, 8 * n1);
+  if (need & NEED_BASES) res->bases = hold.raw<uint64_t>(n1);
+  if (need & NEED_UNIQ) res->uniq = hold.raw<uint32_t>(n1);
+  if (need & NEED_SQ) res->isq = hold.raw<int64_t>(n1);
   if (decimal) {
-    res->dsum = (double*)bg_alloc(c, 8 * n1);
-    if (need_sq) res->dsq = (double*)bg_alloc(c, 8 * n1);
-    if (!res->dsum || (need_sq && !res->dsq)) {
-      bg_result_free(res);
-      return BG_E_NOMEM;
-    }
+    res->dsum = hold.raw<double>(n1);
+    if (need_sq) res->dsq = hold.raw<double>(n1);
   }
   if (faster) need |= NEED_WIN;  // the windows are the sweep's (bg_faster.hip), kept for every use
   if (need & NEED_WIN) {
-    res->wlo = (uint64_t*)bg_alloc(c, 8 * n1);
-    res->whi = (uint64_t*)bg_alloc(c, 8 * n1);
+    res->wlo = hold.raw<uint64_t>(n1);
+    res->whi = hold.raw<uint64_t>(n1);
   }
   res->map_tab = map;
   res->mapfields = mapfields;
   res->perc = perc;
-  if (!res->cnt || ((need & NEED_SUM) && !res->isum) || ((need & NEED_EXT) && (!res->vmin || !res->vmax)) ||
-      ((need & NEED_BASES) && !res->bases) || ((need & NEED_UNIQ) && !res->uniq) ||
-      ((need & NEED_WIN) && (!res->wlo || !res->whi)) || ((need & NEED_SQ) && !res->isq)) {
-    bg_result_free(res);
-    return BG_E_NOMEM;
-  }
+  if (!hold.ok()) return BG_E_NOMEM;
   // zero-length rows change the sweep window under Overlapping(0); RangedDist (--range)
   // treats them as ordinary rows
   if (faster) {
     const uint64_t m1 = M->n ? M->n : 1;
-    res->zin = (int64_t*)bg_alloc(c, 8 * m1);
-    res->zout = (int64_t*)bg_alloc(c, 8 * m1);
-    int rf = (!res->zin || !res->zout) ? BG_E_NOMEM
-                                       : bg_faster_windows(c, R, M, crit, (int64_t)opts->overlap_bp,
-                                                           (int64_t)opts->range_bp, perc, ref == map, res->wlo,
-                                                           res->whi, res->zin, res->zout);
-    if (rf) {
-      bg_result_free(res);
-      return rf;
-    }
+    res->zin = hold.raw<int64_t>(m1);
+    res->zout = hold.raw<int64_t>(m1);
+    if (!hold.ok()) return BG_E_NOMEM;
+    int rf = bg_faster_windows(c, R, M, crit, (int64_t)opts->overlap_bp, (int64_t)opts->range_bp, perc, ref == map,
+                               res->wlo, res->whi, res->zin, res->zout);
+    if (rf) return rf;
   } else if (tiny || (crit != BG_OVR_RANGE && (R->has_zero_len || M->has_zero_len))) {
     int rz = ref == map ? map_zero_prep_single(c, R, res) : tiny ? map_deque_prep(c, R, M, res) : map_zero_prep(c, R, M, res);
-    if (rz) {
-      bg_result_free(res);
-      return rz;
-    }
+    if (rz) return rz;
   }
   MapArgs A;
   A.RS = R->ks;
@@ -1474,10 +1442,7 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
   // and running-double replays enumerate one contiguous window and keep the global bound
   if (M->maxlen > BG_LONG_THR && !res->zin && !decimal && !tmean && !faster) {
     int rl = map_long_rows(c, M, res);
-    if (rl) {
-      bg_result_free(res);
-      return rl;
-    }
+    if (rl) return rl;
     A.lrows = res->lrows;
     if (A.lrows.ncls) A.L = BG_LONG_THR;
   }
@@ -1590,11 +1555,12 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
     uint32_t* ro = nullptr;
     ulonglong2* pk = nullptr;
     uint32_t* pl = nullptr;
+    BgHold he(c);
     if (M->n && M->n < (1ull << 32)) {  // set order of every run of equal map starts
-      ro = (uint32_t*)bg_alloc(c, 4 * M->n);
-      pk = (ulonglong2*)bg_alloc(c, 16 * M->n);
-      pl = (uint32_t*)bg_alloc(c, 4 * M->n);
-      if (!ro || !pk || !pl) rc = BG_E_NOMEM;
+      ro = he.alloc<uint32_t>(M->n);
+      pk = he.alloc<ulonglong2>(M->n);
+      pl = he.alloc<uint32_t>(M->n);
+      if (!he.ok()) rc = BG_E_NOMEM;
       else {
         BG_LAUNCH(c, "k_ev_keys", k_ev_keys, dim3(bg_blocks(M->n, BG_NT)), dim3(BG_NT), E, pk, pl);
         rc = bg_hip_ok(c, hipGetLastError());
@@ -1612,18 +1578,13 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
       else
         rc = map_tmean(c, ecrit, E, res->cnt, opts, res);
     }
-    if (ro || pk || pl) {
-      (void)hipStreamSynchronize(c->stream);
-      bg_release(c, ro);
-      bg_release(c, pk);
-      bg_release(c, pl);
-    }
+    if (ro || pk || pl) (void)hipStreamSynchronize(c->stream);  // before he lets them go
   }
   if (!rc) rc = bg_hip_ok(c, hipMemcpyAsync(c->hstat, c->dstat, sizeof(bg_dstatus), hipMemcpyDeviceToHost, c->stream));
   if (!rc) rc = bg_hip_ok(c, hipStreamSynchronize(c->stream));
   if (!rc && need_rrank && R->n) {  // printed-line ranks for --echo-ref-row-id
-    res->rrank = (uint64_t*)bg_alloc(c, 8 * n1);
-    if (!res->rrank) rc = BG_E_NOMEM;
+    res->rrank = hold.raw<uint64_t>(n1);
+    if (!hold.ok()) rc = BG_E_NOMEM;
     if (!rc) {
       BG_LAUNCH(c, "k_map_printed", k_map_printed, dim3(bg_blocks(R->n, BG_NT)), dim3(BG_NT), res->cnt,
                 R->n, res->rrank);
@@ -1634,14 +1595,12 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
   if (!rc && (c->hstat->flags & 4ULL) && !decimal) {
     // a window sum reached 2^53: the int64 sums are exact where the reference's doubles are
     // not; redo with the reference's running doubles
-    bg_result_free(res);
+    bg_free(c, res);
     return map_impl(c, set, ref, map, opts, out, true);
   }
-  if (rc) {
-    bg_result_free(res);
-    return rc;
-  }
+  if (rc) return rc;
   *out = res;
+  res = nullptr;  // the caller's from here
   bg_mark(c, "map");
   return 0;
 }

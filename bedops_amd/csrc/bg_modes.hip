@@ -73,8 +73,9 @@ __global__ void k_expand(F f, const uint64_t* __restrict__ off, uint64_t n, uint
 template <class F>
 static int expand(bg_ctx* c, const F& f, uint64_t n, Ivl& out, const char* cname,
                   const char* wname) {
-  uint64_t* off = (uint64_t*)bg_alloc(c, 8 * (n + 1));
-  if (!off) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint64_t* off = hold.alloc<uint64_t>(n + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (n) {
     BG_LAUNCH(c, cname, k_each_count<F>, dim3(bg_blocks(n, 256)), dim3(256), f, n, off);
     BG_HIP(c, hipGetLastError());
@@ -89,7 +90,6 @@ static int expand(bg_ctx* c, const F& f, uint64_t n, Ivl& out, const char* cname
               out.s, out.e);
     BG_HIP(c, hipGetLastError());
   }
-  bg_release(c, off);
   return 0;
 }
 
@@ -184,6 +184,7 @@ struct Events {
   uint64_t n = 0;
 };
 
+// (E is owned by the caller's guard)
 static int build_events(bg_ctx* c, const std::vector<Ivl>& lists, Events& E) {
   uint64_t tot = 0;
   for (const Ivl& v : lists) tot += 2 * v.n;
@@ -209,7 +210,7 @@ static int build_events(bg_ctx* c, const std::vector<Ivl>& lists, Events& E) {
   return bg_scan_sum_u64(c, E.dx, E.dx, tot, nullptr);
 }
 
-static void free_events(bg_ctx* c, Events& E) {
+static void bg_free(bg_ctx* c, Events& E) {
   bg_release(c, E.ev);
   bg_release(c, E.dx);
   E = Events();
@@ -406,7 +407,7 @@ struct Multi {
   uint64_t n = 0;
 };
 
-static void multi_free(bg_ctx* c, Multi& m) {
+static void bg_free(bg_ctx* c, Multi& m) {
   bg_release(c, m.s);
   bg_release(c, m.e);
   bg_release(c, m.rp);
@@ -414,6 +415,7 @@ static void multi_free(bg_ctx* c, Multi& m) {
   m = Multi();
 }
 
+// (m is owned by the caller's guard)
 static int multi_alloc(bg_ctx* c, Multi& m, uint64_t n) {
   m.n = n;
   const uint64_t k = n ? n : 1;
@@ -624,11 +626,12 @@ extern "C" int bg_complement(bg_ctx* c, bg_set* set, const int* files, int nf, i
   int rc = bg_check_files(c, set, files, nf, 1);
   if (rc || !out) return rc ? rc : BG_E_ARG;
   Ivl u, g;
+  BgHold hold(c);
+  hold.own(u, g);
   if ((rc = bg_union_components(c, set, files, nf, u))) return rc;
   GapF f{u.s, u.e, full_left};
   if ((rc = expand(c, f, u.n, g, "k_complement_count", "k_complement_write"))) return rc;
-  ivl_free(c, u);
-  *out = bg_new_ivl_result(c, set, g);
+  if ((rc = bg_new_ivl_result(c, set, g, out))) return rc;
   bg_mark(c, "complement");
   return 0;
 }
@@ -639,11 +642,12 @@ extern "C" int bg_chop(bg_ctx* c, bg_set* set, const int* files, int nf, uint64_
   if (rc || !out) return rc ? rc : BG_E_ARG;
   if (chunk == 0) return bg_fail(c, BG_E_ARG, "bp setting for chop must be > 0");
   Ivl u, g;
+  BgHold hold(c);
+  hold.own(u, g);
   if ((rc = bg_union_components(c, set, files, nf, u))) return rc;
   ChopF f{u.s, u.e, chunk, stagger ? stagger : chunk, exclude_short};
   if ((rc = expand(c, f, u.n, g, "k_chop_count", "k_chop_write"))) return rc;
-  ivl_free(c, u);
-  *out = bg_new_ivl_result(c, set, g);
+  if ((rc = bg_new_ivl_result(c, set, g, out))) return rc;
   bg_mark(c, "chop");
   return 0;
 }
@@ -655,12 +659,13 @@ extern "C" int bg_partition(bg_ctx* c, bg_set* set, const int* files, int nf, bg
   std::vector<Ivl> lists;
   for (int k = 0; k < nf; ++k) lists.push_back(bg_table_ivl(set->t[files[k]]));
   Events E;
+  Ivl g;
+  BgHold hold(c);
+  hold.own(E, g);
   if ((rc = build_events(c, lists, E))) return rc;
   PartF f{EvView{E.ev, E.dx, E.n}};
-  Ivl g;
   if ((rc = expand(c, f, E.n, g, "k_partition_count", "k_partition_write"))) return rc;
-  free_events(c, E);
-  *out = bg_new_ivl_result(c, set, g);
+  if ((rc = bg_new_ivl_result(c, set, g, out))) return rc;
   bg_mark(c, "partition");
   return 0;
 }
@@ -670,9 +675,11 @@ extern "C" int bg_partition(bg_ctx* c, bg_set* set, const int* files, int nf, bg
 static int symmdiff_replay(bg_ctx* c, bg_set* set, const int* files, int nf, bg_result** out) {
   int rc;
   std::vector<Ivl> comps(nf);
+  Ivl u, g;
+  BgHold hold(c);
+  hold.own(comps, u, g);
   for (int k = 0; k < nf; ++k)
     if ((rc = bg_table_components(c, set->t[files[k]], comps[k]))) return rc;
-  Ivl u;
   if ((rc = bg_union_components(c, set, files, nf, u))) return rc;
   std::vector<SdFile> hf(nf);
   for (int k = 0; k < nf; ++k) hf[k] = SdFile{comps[k].s, comps[k].e, comps[k].n};
@@ -680,11 +687,11 @@ static int symmdiff_replay(bg_ctx* c, bg_set* set, const int* files, int nf, bg_
   // threads: one per segment, capped so the per-thread reader states stay within 64 MiB
   const uint64_t cap = std::max<uint64_t>(256, (64ull << 20) / (sizeof(SdRd) * (uint64_t)nf));
   const uint64_t nthr = std::min<uint64_t>(nseg, cap);
-  SdFile* df = (SdFile*)bg_alloc(c, sizeof(SdFile) * nf);
-  SdRd* scr = (SdRd*)bg_alloc(c, sizeof(SdRd) * (nthr ? nthr : 1) * nf);
-  uint64_t* off = (uint64_t*)bg_alloc(c, 8 * (nseg + 1));
-  int* err = (int*)bg_alloc(c, 8);
-  if (!df || !scr || !off || !err) return BG_E_NOMEM;
+  SdFile* df = hold.alloc<SdFile>(nf);
+  SdRd* scr = hold.alloc<SdRd>((nthr ? nthr : 1) * nf);
+  uint64_t* off = hold.alloc<uint64_t>(nseg + 1);
+  int* err = hold.alloc<int>(2);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemcpyAsync(df, hf.data(), sizeof(SdFile) * nf, hipMemcpyHostToDevice, c->stream));
   BG_HIP(c, hipMemsetAsync(err, 0, 8, c->stream));
   if (nthr) {
@@ -696,7 +703,6 @@ static int symmdiff_replay(bg_ctx* c, bg_set* set, const int* files, int nf, bg_
   rc = bg_scan_sum_u64(c, off, off, nseg, off + nseg);
   uint64_t total = 0;
   if (!rc) rc = bg_fetch_u64(c, off + nseg, &total);
-  Ivl g;
   if (!rc) rc = ivl_alloc(c, g, total);
   if (rc) return rc;
   if (nthr) {
@@ -708,14 +714,8 @@ static int symmdiff_replay(bg_ctx* c, bg_set* set, const int* files, int nf, bg_
   int herr = 0;
   BG_HIP(c, hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  for (Ivl& v : comps) ivl_free(c, v);
-  ivl_free(c, u);
-  for (void* p : {(void*)df, (void*)scr, (void*)off, (void*)err}) bg_release(c, p);
-  if (herr) {
-    ivl_free(c, g);
-    return bg_fail(c, BG_E_HIP, "symmdiff replay: push-back stack overflow");
-  }
-  *out = bg_new_ivl_result(c, set, g);
+  if (herr) return bg_fail(c, BG_E_HIP, "symmdiff replay: push-back stack overflow");
+  if ((rc = bg_new_ivl_result(c, set, g, out))) return rc;
   bg_mark(c, "symmdiff");
   return 0;
 }
@@ -728,46 +728,45 @@ extern "C" int bg_symmdiff(bg_ctx* c, bg_set* set, const int* files, int nf, bg_
   for (int k = 0; k < nf; ++k)
     if (set->t[files[k]]->has_zero_len) return symmdiff_replay(c, set, files, nf, out);
   std::vector<Ivl> comps(nf);
+  Events E;
+  Ivl g;
+  BgHold hold(c);
+  hold.own(comps, E, g);
   for (int k = 0; k < nf; ++k)
     if ((rc = bg_table_components(c, set->t[files[k]], comps[k]))) return rc;
-  Events E;
   if ((rc = build_events(c, comps, E))) return rc;
-  for (Ivl& v : comps) ivl_free(c, v);
+  bg_free(c, comps);
   EvView v{E.ev, E.dx, E.n};
-  uint8_t* f = (uint8_t*)bg_alloc(c, E.n ? E.n : 1);
-  if (!f) return BG_E_NOMEM;
+  uint8_t* f = hold.alloc<uint8_t>(E.n ? E.n : 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (E.n) {
     BG_LAUNCH(c, "k_last_flags", k_last_flags, dim3(bg_blocks(E.n, 256)), dim3(256), v, f);
     BG_HIP(c, hipGetLastError());
   }
   uint64_t *U = nullptr, nu = 0;
   if ((rc = bg_compact_flags(c, f, E.n, &U, &nu))) return rc;
-  bg_release(c, f);
-  uint8_t* fo = (uint8_t*)bg_alloc(c, nu ? nu : 1);
-  uint8_t* fc = (uint8_t*)bg_alloc(c, nu ? nu : 1);
-  if (!fo || !fc) return BG_E_NOMEM;
+  hold(U);
+  hold.drop(f);
+  uint8_t* fo = hold.alloc<uint8_t>(nu ? nu : 1);
+  uint8_t* fc = hold.alloc<uint8_t>(nu ? nu : 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (nu) {
     BG_LAUNCH(c, "k_sd_flags", k_sd_flags, dim3(bg_blocks(nu, 256)), dim3(256), v, U, nu, fo, fc);
     BG_HIP(c, hipGetLastError());
   }
   uint64_t *O = nullptr, *C = nullptr, no = 0, ncl = 0;
   if ((rc = bg_compact_flags(c, fo, nu, &O, &no))) return rc;
+  hold(O);
   if ((rc = bg_compact_flags(c, fc, nu, &C, &ncl))) return rc;
+  hold(C);
   if (no != ncl) return bg_fail(c, BG_E_ARG, "symmdiff: unbalanced coverage events");
-  Ivl g;
   if ((rc = ivl_alloc(c, g, no))) return rc;
   if (no) {
     BG_LAUNCH(c, "k_sd_out", k_sd_out, dim3(bg_blocks(no, 256)), dim3(256), v, U, O, C, no, g.s,
               g.e);
     BG_HIP(c, hipGetLastError());
   }
-  bg_release(c, fo);
-  bg_release(c, fc);
-  bg_release(c, U);
-  bg_release(c, O);
-  bg_release(c, C);
-  free_events(c, E);
-  *out = bg_new_ivl_result(c, set, g);
+  if ((rc = bg_new_ivl_result(c, set, g, out))) return rc;
   bg_mark(c, "symmdiff");
   return 0;
 }
@@ -789,27 +788,26 @@ extern "C" int bg_everything(bg_ctx* c, bg_set* set, const int* files, int nf, b
     return 0;
   };
   Multi acc;
+  BgHold hold(c);
+  hold.own(acc);
   if ((rc = load(set->t[files[0]], acc))) return rc;
   for (int k = 1; k < nf; ++k) {
     Multi y, z;
+    BgHold hk(c);
+    hk.own(y, z);
     if ((rc = load(set->t[files[k]], y))) return rc;
     if ((rc = multi_alloc(c, z, acc.n + y.n))) return rc;
     if (z.n) {
-      uint8_t* fy = (uint8_t*)bg_alloc(c, z.n);
-      uint64_t* tp = (uint64_t*)bg_alloc(c, 8 * z.n);
-      uint32_t* tl = (uint32_t*)bg_alloc(c, 4 * z.n);
-      if (!fy || !tp || !tl) return BG_E_NOMEM;
+      uint8_t* fy = hk.alloc<uint8_t>(z.n);
+      uint64_t* tp = hk.alloc<uint64_t>(z.n);
+      uint32_t* tl = hk.alloc<uint32_t>(z.n);
+      if (!hk.ok()) return BG_E_NOMEM;
       BG_LAUNCH(c, "k_umerge", k_umerge, dim3(bg_blocks(z.n, 256)), dim3(256), acc, y, z, fy);
       BG_HIP(c, hipGetLastError());
       BG_LAUNCH(c, "k_ufix", k_ufix, dim3(bg_blocks(z.n, 256)), dim3(256), z, fy, tp, tl);
       BG_HIP(c, hipGetLastError());
-      bg_release(c, fy);
-      bg_release(c, tp);
-      bg_release(c, tl);
     }
-    multi_free(c, acc);
-    multi_free(c, y);
-    acc = z;
+    std::swap(acc, z);  // the previous merge and y leave with hk
   }
   *out = new_multi_result(c, set, acc);
   bg_mark(c, "everything");
@@ -831,21 +829,22 @@ extern "C" int bg_set_pad(bg_ctx* c, bg_set* set, int file, int lpad, int rpad) 
   P.first_only = (P.mode == 0 && lpad < 0) ? 1 : 0;
   P.brk = ~0ull;
   int rc = 0;
+  BgHold hold(c);
   if (n && P.first_only) {
-    unsigned long long* d = (unsigned long long*)bg_alloc(c, 8);
-    if (!d) return BG_E_NOMEM;
+    unsigned long long* d = hold.alloc<unsigned long long>(1);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_HIP(c, hipMemsetAsync(d, 0xff, 8, c->stream));
     BG_LAUNCH(c, "k_pad_break", k_pad_break, dim3(bg_blocks(n, 256)), dim3(256), T->ks, T->ke, n, P,
               d);
     BG_HIP(c, hipGetLastError());
     if ((rc = bg_fetch_u64(c, (const uint64_t*)d, &P.brk))) return rc;
-    bg_release(c, d);
+    hold.drop(d);
   }
-  int64_t* ns = (int64_t*)bg_alloc(c, 8 * (n ? n : 1));
-  int64_t* ne = (int64_t*)bg_alloc(c, 8 * (n ? n : 1));
-  uint8_t* keep = (uint8_t*)bg_alloc(c, n ? n : 1);
-  uint8_t* clamp = (uint8_t*)bg_alloc(c, n ? n : 1);
-  if (!ns || !ne || !keep || !clamp) return BG_E_NOMEM;
+  int64_t* ns = hold.alloc<int64_t>(n ? n : 1);
+  int64_t* ne = hold.alloc<int64_t>(n ? n : 1);
+  uint8_t* keep = hold.alloc<uint8_t>(n ? n : 1);
+  uint8_t* clamp = hold.alloc<uint8_t>(n ? n : 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemsetAsync(&c->dstat->first_bad, 0xff, 8, c->stream));
   if (n) {
     BG_LAUNCH(c, "k_pad_eval", k_pad_eval, dim3(bg_blocks(n, 256)), dim3(256), T->ks, T->ke, n, P,
@@ -855,6 +854,7 @@ extern "C" int bg_set_pad(bg_ctx* c, bg_set* set, int file, int lpad, int rpad) 
   uint64_t* K = nullptr;
   uint64_t nk = 0;
   if ((rc = bg_compact_flags(c, keep, n, &K, &nk))) return rc;  // synchronises
+  hold(K);
   BG_HIP(c, hipMemcpyAsync(c->hstat, c->dstat, sizeof(bg_dstatus), hipMemcpyDeviceToHost, c->stream));
   BG_HIP(c, hipStreamSynchronize(c->stream));
   if (c->hstat->first_bad != ~0ULL)
@@ -864,8 +864,8 @@ extern "C" int bg_set_pad(bg_ctx* c, bg_set* set, int file, int lpad, int rpad) 
   // compact every column by the kept rows
   auto gather = [&](auto* src, auto*& dst) -> int {
     using T0 = std::remove_reference_t<decltype(*src)>;
-    dst = (T0*)bg_alloc(c, sizeof(T0) * (nk ? nk : 1));
-    if (!dst) return BG_E_NOMEM;
+    dst = hold.alloc<T0>(nk ? nk : 1);
+    if (!hold.ok()) return BG_E_NOMEM;
     if (nk) {
       BG_LAUNCH(c, "k_gather", k_gather<T0>, dim3(bg_blocks(nk, 256)), dim3(256), src, K, nk, dst);
       BG_HIP(c, hipGetLastError());
@@ -880,21 +880,18 @@ extern "C" int bg_set_pad(bg_ctx* c, bg_set* set, int file, int lpad, int rpad) 
   if ((rc = gather(ns, gks)) || (rc = gather(ne, gke)) || (rc = gather(clamp, gcl))) return rc;
   if (T->rest_off && ((rc = gather(T->rest_off, gro)) || (rc = gather(T->rest_len, grl)))) return rc;
   if (T->score && (rc = gather(T->score, gsc))) return rc;
-  bg_release(c, ns);
-  bg_release(c, ne);
-  bg_release(c, keep);
-  bg_release(c, clamp);
-  bg_release(c, K);
+  hold.drop(ns, ne, keep, clamp, K);
   // rows clamped to base 0: stable re-sort by (chromosome, end) within their slots
   uint64_t* pos = nullptr;
   uint64_t m = 0;
   if ((rc = bg_compact_flags(c, gcl, nk, &pos, &m))) return rc;
-  bg_release(c, gcl);
+  hold(pos);
+  hold.drop(gcl);
   if (m > 1) {
     if (m > 0xffffffffull) return bg_fail(c, BG_E_UNSUPPORTED, "--range: too many rows at base 0");
-    uint64_t* key = (uint64_t*)bg_alloc(c, 8 * m);
-    uint32_t* perm = (uint32_t*)bg_alloc(c, 4 * m);
-    if (!key || !perm) return BG_E_NOMEM;
+    uint64_t* key = hold.alloc<uint64_t>(m);
+    uint32_t* perm = hold.alloc<uint32_t>(m);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_LAUNCH(c, "k_clamp_keys", k_clamp_keys, dim3(bg_blocks(m, 256)), dim3(256), gke, pos, m, key,
               perm);
     BG_HIP(c, hipGetLastError());
@@ -902,37 +899,33 @@ extern "C" int bg_set_pad(bg_ctx* c, bg_set* set, int file, int lpad, int rpad) 
     auto permute = [&](auto*& col) -> int {
       using T0 = std::remove_reference_t<decltype(*col)>;
       if (!col) return 0;
-      T0* dst = (T0*)bg_alloc(c, sizeof(T0) * nk);
-      if (!dst) return BG_E_NOMEM;
+      T0* dst = hold.alloc<T0>(nk);
+      if (!hold.ok()) return BG_E_NOMEM;
       BG_HIP(c, hipMemcpyAsync(dst, col, sizeof(T0) * nk, hipMemcpyDeviceToDevice, c->stream));
       BG_LAUNCH(c, "k_permute_slots", k_permute_slots<T0>, dim3(bg_blocks(m, 256)), dim3(256), col,
                 pos, perm, m, dst);
       BG_HIP(c, hipGetLastError());
-      bg_release(c, col);
+      hold.drop(col);
       col = dst;
       return 0;
     };
     if ((rc = permute(gke)) || (rc = permute(gro)) || (rc = permute(grl)) || (rc = permute(gsc)))
       return rc;
-    bg_release(c, key);
-    bg_release(c, perm);
+    hold.drop(key, perm);
   }
-  bg_release(c, pos);
-  bg_release(c, T->ks);
-  bg_release(c, T->ke);
-  bg_release(c, T->rest_off);
-  bg_release(c, T->rest_len);
-  bg_release(c, T->score);
-  T->ks = gks;
-  T->ke = gke;
-  T->rest_off = gro;
-  T->rest_len = grl;
-  T->score = gsc;
+  hold.drop(pos);
+  // the table takes the padded columns; its old ones leave with the guard
+  hold(T->ks), hold(T->ke), hold(T->rest_off), hold(T->rest_len), hold(T->score);
+  T->ks = hold.give(gks);
+  T->ke = hold.give(gke);
+  T->rest_off = hold.give(gro);
+  T->rest_len = hold.give(grl);
+  T->score = hold.give(gsc);
   T->n = nk;
   // row statistics and chromosome runs of the padded rows
-  unsigned long long* st = (unsigned long long*)bg_alloc(c, 24);
-  uint8_t* f = (uint8_t*)bg_alloc(c, nk ? nk : 1);
-  if (!st || !f) return BG_E_NOMEM;
+  unsigned long long* st = hold.alloc<unsigned long long>(3);
+  uint8_t* f = hold.alloc<uint8_t>(nk ? nk : 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemsetAsync(st, 0, 24, c->stream));
   if (nk) {
     BG_LAUNCH(c, "k_row_stats", k_row_stats, dim3(bg_blocks(nk, 256)), dim3(256), T->ks, T->ke, nk, st);
@@ -942,10 +935,11 @@ extern "C" int bg_set_pad(bg_ctx* c, bg_set* set, int file, int lpad, int rpad) 
   uint64_t* R = nullptr;
   uint64_t nr = 0;
   if ((rc = bg_compact_flags(c, f, nk, &R, &nr))) return rc;
+  hold(R);
   std::vector<uint64_t> hrow(nr);
   std::vector<int64_t> hkey(nr);
-  int64_t* rk = (int64_t*)bg_alloc(c, 8 * (nr ? nr : 1));
-  if (!rk) return BG_E_NOMEM;
+  int64_t* rk = hold.alloc<int64_t>(nr ? nr : 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (nr) {
     BG_LAUNCH(c, "k_gather", k_gather<int64_t>, dim3(bg_blocks(nr, 256)), dim3(256), T->ks, R, nr, rk);
     BG_HIP(c, hipGetLastError());
@@ -961,10 +955,6 @@ extern "C" int bg_set_pad(bg_ctx* c, bg_set* set, int file, int lpad, int rpad) 
   T->run_row0.push_back(nk);
   T->run_name.clear();
   for (uint64_t k = 0; k < nr; ++k) T->run_name.push_back(set->names[(size_t)(hkey[k] >> BG_KEY_SHIFT)]);
-  bg_release(c, st);
-  bg_release(c, f);
-  bg_release(c, R);
-  bg_release(c, rk);
   if (hst[2]) return bg_fail(c, BG_E_UNSORTED, "--range: padded rows are out of order");
   return 0;
 }

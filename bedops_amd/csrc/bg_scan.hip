@@ -63,8 +63,9 @@ static int scan_impl(bg_ctx* c, const T* in, T* out, uint64_t n, Op op, T identi
     BG_HIP(c, hipGetLastError());
     return 0;
   }
-  T* part = (T*)bg_alloc(c, sizeof(T) * nb);
-  if (!part) return BG_E_NOMEM;
+  BgHold hold(c);
+  T* part = hold.alloc<T>(nb);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_tile_reduce", (k_tile_reduce<T, Op>), dim3(nb), dim3(BG_NT), in, n, part,
                      op, identity);
   BG_HIP(c, hipGetLastError());
@@ -73,7 +74,6 @@ static int scan_impl(bg_ctx* c, const T* in, T* out, uint64_t n, Op op, T identi
   BG_LAUNCH(c, "k_tile_scan", (k_tile_scan<T, Op>), dim3(nb), dim3(BG_NT), in, out, n,
                      (const T*)part, op, identity, d_total);
   BG_HIP(c, hipGetLastError());
-  bg_release(c, part);
   return 0;
 }
 

@@ -592,6 +592,7 @@ void ivl_free(bg_ctx* c, Ivl& v) {
   v = Ivl();
 }
 
+// the caller owns v (BgHold::own) before it is filled, here or by a function that fills it
 int ivl_alloc(bg_ctx* c, Ivl& v, uint64_t n) {
   v.n = n;
   v.s = (int64_t*)bg_alloc(c, 8 * (n ? n : 1));
@@ -668,36 +669,41 @@ __global__ void __launch_bounds__(BG_NT) k_compact_rows_bytes(const uint8_t* __r
 int bg_compact_flags(bg_ctx* c, const uint8_t* flag, uint64_t n, uint64_t** rows, uint64_t* total) {
   const unsigned nb = bg_blocks(n, CF_TILE);
   *rows = nullptr;
-  return count_scan_write(
+  BgHold hold(c);
+  uint64_t* out = nullptr;
+  const int rc = count_scan_write(
       c, nb,
       [&](uint64_t* cnt) {
         BG_LAUNCH(c, "k_compact_flags_count", k_compact_flags<false>, dim3(nb), dim3(BG_NT), flag,
                   n, cnt, (const uint64_t*)nullptr, (uint64_t*)nullptr);
       },
       [&](uint64_t* off, uint64_t tot) -> int {
-        *rows = (uint64_t*)bg_alloc(c, 8 * (tot ? tot : 1));
-        if (!*rows) return BG_E_NOMEM;
+        out = hold.alloc<uint64_t>(tot ? tot : 1);
+        if (!hold.ok()) return BG_E_NOMEM;
         if (nb)
           BG_LAUNCH(c, "k_compact_flags_write", k_compact_flags<true>, dim3(nb), dim3(BG_NT), flag,
-                    n, (uint64_t*)nullptr, off, *rows);
+                    n, (uint64_t*)nullptr, off, out);
         return 0;
       },
       total);
+  if (!rc) *rows = hold.give(out);
+  return rc;
 }
 
 int bg_components(bg_ctx* c, const Ivl& in, Ivl& out) {
   const uint64_t n = in.n;
   if (n == 0) return ivl_alloc(c, out, 0);
   const unsigned nb = bg_blocks(n, CT_TILE);
-  int64_t* carry = (int64_t*)bg_alloc(c, 8ull * nb);
-  if (!carry) return BG_E_NOMEM;
+  BgHold hold(c);
+  int64_t* carry = hold.alloc<int64_t>(nb);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_tile_max", k_tile_max, dim3(bg_blocks(nb, TM_TILES)), dim3(BG_NT), in.e, n, nb,
             carry);
   BG_HIP(c, hipGetLastError());
   int rc = bg_scan_max_i64(c, carry, carry, nb, LLONG_MIN);
   if (rc) return rc;
   uint64_t total = 0;
-  rc = count_scan_write(
+  return count_scan_write(
       c, nb,
       [&](uint64_t* cnt) {
         BG_LAUNCH(c, "k_components_count", k_components<false>, dim3(nb), dim3(BG_NT), in.s, in.e,
@@ -711,8 +717,6 @@ int bg_components(bg_ctx* c, const Ivl& in, Ivl& out) {
         return 0;
       },
       &total);
-  bg_release(c, carry);
-  return rc;
 }
 
 static int merge_sorted(bg_ctx* c, const Ivl& x, const Ivl& y, Ivl& z) {
@@ -734,17 +738,18 @@ static int mp_op(bg_ctx* c, const Ivl& x, const Ivl& y, Ivl& out, const char* cn
   const uint64_t nz = x.n + y.n;
   const unsigned nb = bg_blocks(nz, MP_TILE);
   if (nb == 0) return ivl_alloc(c, out, 0);
-  uint64_t* part = (uint64_t*)bg_alloc(c, 8ull * (nb + 1));
-  if (!part) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint64_t* part = hold.alloc<uint64_t>(nb + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   const int64_t* yk = (MODE == MP_INTERSECT) ? y.s : y.e;
   BG_LAUNCH(c, "k_mp_partition", k_mp_partition, dim3(bg_blocks(nb + 1, 256)), dim3(256), x.s, x.n,
             yk, y.n, nb, part);
   BG_HIP(c, hipGetLastError());
   if (seg_names) {
     int rc = ivl_alloc(c, out, nz);
-    out.seg_off = (uint64_t*)bg_alloc(c, 8ull * (nb + 1));
-    out.seg_boff = (uint64_t*)bg_alloc(c, 8ull * (nb + 1));
-    if (rc || !out.seg_off || !out.seg_boff) return BG_E_NOMEM;
+    out.seg_off = hold.raw<uint64_t>(nb + 1);
+    out.seg_boff = hold.raw<uint64_t>(nb + 1);
+    if (rc || !hold.ok()) return BG_E_NOMEM;
     out.nseg = nb;
     BG_LAUNCH(c, wname, (k_mp_tile<MODE, true, true>), dim3(nb), dim3(BG_NT), x.s, x.e, x.n, y.s, y.e,
               y.n, part, out.seg_off, (const uint64_t*)nullptr, out.s, out.e, seg_names, out.seg_boff);
@@ -756,11 +761,10 @@ static int mp_op(bg_ctx* c, const Ivl& x, const Ivl& y, Ivl& out, const char* cn
     out.n = 0;
     out.seg_nz = nz;
     out.n_pending = true;
-    bg_release(c, part);
     return 0;
   }
   uint64_t total = 0;
-  int rc = count_scan_write(
+  return count_scan_write(
       c, nb,
       [&](uint64_t* cnt) {
         BG_LAUNCH(c, cname, (k_mp_tile<MODE, false>), dim3(nb), dim3(BG_NT), x.s, x.e, x.n, y.s, y.e,
@@ -774,8 +778,6 @@ static int mp_op(bg_ctx* c, const Ivl& x, const Ivl& y, Ivl& out, const char* cn
         return 0;
       },
       &total);
-  bg_release(c, part);
-  return rc;
 }
 
 Ivl bg_table_ivl(bg_table* T) {
@@ -809,35 +811,33 @@ int bg_need_rows(bg_ctx* c, bg_set* set, const int* files, int nf, const char* w
 
 // components of the union of the given tables
 int bg_union_components(bg_ctx* c, bg_set* set, const int* files, int nf, Ivl& out) {
-  Ivl acc;
-  int rc = bg_table_components(c, set->t[files[0]], acc);
+  int rc = bg_table_components(c, set->t[files[0]], out);
   if (rc) return rc;
   for (int k = 1; k < nf; ++k) {
-    Ivl ck, z, m;
+    Ivl ck, z;
+    BgHold hold(c);
+    hold.own(ck, z);
     if ((rc = bg_table_components(c, set->t[files[k]], ck))) return rc;
-    if ((rc = merge_sorted(c, acc, ck, z))) return rc;
-    ivl_free(c, acc);
+    if ((rc = merge_sorted(c, out, ck, z))) return rc;
+    ivl_free(c, out);
     ivl_free(c, ck);
-    if ((rc = bg_components(c, z, m))) return rc;
-    ivl_free(c, z);
-    acc = m;
+    if ((rc = bg_components(c, z, out))) return rc;
   }
-  out = acc;
   return 0;
 }
 
-bg_result* bg_new_ivl_result(bg_ctx* c, bg_set* set, Ivl& v) {
+int bg_new_ivl_result(bg_ctx* c, bg_set* set, Ivl& v, bg_result** out) {
+  Ivl w;
+  BgHold hold(c);
+  hold.own(w);
   if (!v.owned && v.s) {  // a view of a table's set: the result gets its own copy
-    Ivl w;
-    if (ivl_alloc(c, w, v.n)) return nullptr;
+    if (ivl_alloc(c, w, v.n)) return BG_E_NOMEM;
     if (v.n) {
-      if (hipMemcpyAsync(w.s, v.s, 8 * v.n, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-          hipMemcpyAsync(w.e, v.e, 8 * v.n, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
-        ivl_free(c, w);
-        return nullptr;
-      }
+      BG_HIP(c, hipMemcpyAsync(w.s, v.s, 8 * v.n, hipMemcpyDeviceToDevice, c->stream));
+      BG_HIP(c, hipMemcpyAsync(w.e, v.e, 8 * v.n, hipMemcpyDeviceToDevice, c->stream));
     }
     v = w;
+    w = Ivl();
   }
   bg_result* r = new bg_result();
   r->ctx = c;
@@ -851,8 +851,9 @@ bg_result* bg_new_ivl_result(bg_ctx* c, bg_set* set, Ivl& v) {
   r->seg_boff = v.seg_boff;
   r->seg_nz = v.seg_nz;
   r->n_pending = v.n_pending;
-  v.owned = false;
-  return r;
+  v = Ivl();
+  *out = r;
+  return 0;
 }
 
 // segment t's pieces -> [seg_off[t], seg_off[t+1]) of contiguous s/e
@@ -878,22 +879,18 @@ int bg_result_compact(bg_ctx* c, bg_result* r) {
   int rc = bg_result_resolve_n(c, r);
   if (rc) return rc;
   Ivl w;
-  if (ivl_alloc(c, w, r->n)) {
-    ivl_free(c, w);
-    return BG_E_NOMEM;
-  }
+  BgHold hold(c);
+  hold.own(w);
+  if (ivl_alloc(c, w, r->n)) return BG_E_NOMEM;
   BG_LAUNCH(c, "k_seg_compact", k_seg_compact, dim3((unsigned)r->nseg), dim3(BG_NT), r->s, r->e, r->seg_off,
             w.s, w.e);
   BG_HIP(c, hipGetLastError());
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  bg_release(c, r->s);
-  bg_release(c, r->e);
-  bg_release(c, r->seg_off);
-  bg_release(c, r->seg_boff);
-  r->s = w.s;
-  r->e = w.e;
+  std::swap(r->s, w.s);  // w leaves with the segmented blocks
+  std::swap(r->e, w.e);
+  std::swap(r->seg_off, w.seg_off);
+  std::swap(r->seg_boff, w.seg_boff);
   r->nseg = 0;
-  r->seg_off = r->seg_boff = nullptr;
   return 0;
 }
 
@@ -908,9 +905,10 @@ extern "C" int bg_merge(bg_ctx* c, bg_set* set, const int* files, int nf, bg_res
   int rc = bg_check_files(c, set, files, nf, 1);
   if (rc) return rc;
   Ivl m;
+  BgHold hold(c);
+  hold.own(m);
   if ((rc = bg_union_components(c, set, files, nf, m))) return rc;
-  *out = bg_new_ivl_result(c, set, m);
-  if (!*out) return BG_E_NOMEM;
+  if ((rc = bg_new_ivl_result(c, set, m, out))) return rc;
   bg_mark(c, "merge");
   return 0;
 }
@@ -919,8 +917,11 @@ extern "C" int bg_merge(bg_ctx* c, bg_set* set, const int* files, int nf, bg_res
 static int intersect_zero_len(bg_ctx* c, const std::vector<Ivl>& F, Ivl& acc) {
   const int nf = (int)F.size();
   const uint64_t no = acc.n;
-  uint8_t* flag = (uint8_t*)bg_alloc(c, no + 1);
-  if (!flag) return BG_E_NOMEM;
+  Ivl out;
+  BgHold hold(c);
+  hold.own(out);
+  uint8_t* flag = hold.alloc<uint8_t>(no + 1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemsetAsync(flag, 0, no + 1, c->stream));
   uint64_t npieces = 0;
   for (const Ivl& f : F) {
@@ -933,19 +934,17 @@ static int intersect_zero_len(bg_ctx* c, const std::vector<Ivl>& F, Ivl& acc) {
   uint64_t* anchors = nullptr;
   uint64_t na = 0;
   int rc = bg_compact_flags(c, flag, no + 1, &anchors, &na);
-  bg_release(c, flag);
+  hold.drop(flag);
   if (rc) return rc;
-  if (na == 0) {
-    bg_release(c, anchors);
-    return 0;
-  }
+  hold(anchors);
+  if (na == 0) return 0;
   std::vector<ZFile> hf(nf);
   for (int f = 0; f < nf; ++f) hf[f] = ZFile{F[f].s, F[f].e, F[f].n};
-  ZFile* dF = (ZFile*)bg_alloc(c, sizeof(ZFile) * nf);
-  uint64_t* H = (uint64_t*)bg_alloc(c, 8ull * na * nf);
-  uint64_t* cnt = (uint64_t*)bg_alloc(c, 8ull * (na + 1));
-  uint64_t* bad = (uint64_t*)bg_alloc(c, 8);
-  if (!dF || !H || !cnt || !bad) return BG_E_NOMEM;
+  ZFile* dF = hold.alloc<ZFile>(nf);
+  uint64_t* H = hold.alloc<uint64_t>(na * nf);
+  uint64_t* cnt = hold.alloc<uint64_t>(na + 1);
+  uint64_t* bad = hold.alloc<uint64_t>(1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemcpyAsync(dF, hf.data(), sizeof(ZFile) * nf, hipMemcpyHostToDevice, c->stream));
   BG_HIP(c, hipMemsetAsync(bad, 0, 8, c->stream));
   // every loop iteration of a replay advances a head or restarts from a later piece
@@ -961,7 +960,6 @@ static int intersect_zero_len(bg_ctx* c, const std::vector<Ivl>& F, Ivl& acc) {
   if (hbad)
     return bg_fail(c, BG_E_INTERNAL, "intersect: zero-length replay inconsistent (code " +
                                          std::to_string(hbad) + ")");
-  Ivl out;
   if ((rc = ivl_alloc(c, out, no + total))) return rc;
   BG_LAUNCH(c, "k_zi_replay_write", k_zi_replay<true>, dim3(nb), dim3(BG_NT), dF, nf, acc.s, acc.e,
             no, anchors, na, H, (uint64_t*)nullptr, (const uint64_t*)cnt, out.s, out.e, cap,
@@ -970,14 +968,8 @@ static int intersect_zero_len(bg_ctx* c, const std::vector<Ivl>& F, Ivl& acc) {
     BG_LAUNCH(c, "k_zi_place", k_zi_place, dim3(bg_blocks(no, BG_NT)), dim3(BG_NT), acc.s, acc.e, no,
               anchors, na, (const uint64_t*)cnt, out.s, out.e);
   BG_HIP(c, hipGetLastError());
-  BG_HIP(c, hipStreamSynchronize(c->stream));  // hf/dF copy and the scratch below
-  bg_release(c, dF);
-  bg_release(c, H);
-  bg_release(c, cnt);
-  bg_release(c, bad);
-  bg_release(c, anchors);
-  ivl_free(c, acc);
-  acc = out;
+  BG_HIP(c, hipStreamSynchronize(c->stream));  // hf/dF copy and the scratch held above
+  std::swap(acc, out);  // the old acc leaves with the guard
   return 0;
 }
 
@@ -989,25 +981,28 @@ extern "C" int bg_intersect(bg_ctx* c, bg_set* set, const int* files, int nf, bg
   // zero-length prints afterwards (intersect_zero_len).
   bool zero = false;
   std::vector<Ivl> comp(nf);
+  Ivl acc;
+  BgHold hold(c);
+  hold.own(comp, acc);
   for (int k = 0; k < nf; ++k) {
     zero = zero || set->t[files[k]]->has_zero_len;
     if ((rc = bg_table_components(c, set->t[files[k]], comp[k]))) return rc;
   }
-  Ivl acc = comp[0];
+  acc = comp[0];
   acc.owned = false;  // comp[0] keeps ownership
   for (int k = 1; k < nf; ++k) {
     Ivl p;
+    BgHold hp(c);
+    hp.own(p);
     // the last fold goes straight to the formatter, segmented (unless the zero-length
     // replay still reads it)
     const uint32_t* seg = (k + 1 == nf && !zero) ? set->d_name_len : nullptr;
     if ((rc = mp_op<MP_INTERSECT>(c, acc, comp[k], p, "k_intersect_count", "k_intersect_write", seg)))
       return rc;
-    ivl_free(c, acc);
-    acc = p;
+    std::swap(acc, p);  // the previous fold leaves with hp
   }
   if (zero && (rc = intersect_zero_len(c, comp, acc))) return rc;
-  for (Ivl& v : comp) ivl_free(c, v);
-  *out = bg_new_ivl_result(c, set, acc);
+  if ((rc = bg_new_ivl_result(c, set, acc, out))) return rc;
   bg_mark(c, "intersect");
   return 0;
 }
@@ -1018,13 +1013,13 @@ extern "C" int bg_difference(bg_ctx* c, bg_set* set, int ref, const int* others,
   if (rc) return rc;
   if (ref < 0 || ref >= (int)set->t.size()) return BG_E_ARG;
   Ivl r, o, d;
+  BgHold hold(c);
+  hold.own(r, o, d);
   if ((rc = bg_table_components(c, set->t[ref], r))) return rc;
   if ((rc = bg_union_components(c, set, others, no, o))) return rc;
   if ((rc = mp_op<MP_DIFFERENCE>(c, r, o, d, "k_difference_count", "k_difference_write", set->d_name_len)))
     return rc;
-  ivl_free(c, r);
-  ivl_free(c, o);
-  *out = bg_new_ivl_result(c, set, d);
+  if ((rc = bg_new_ivl_result(c, set, d, out))) return rc;
   bg_mark(c, "difference");
   return 0;
 }
@@ -1037,15 +1032,16 @@ extern "C" int bg_element_of(bg_ctx* c, bg_set* set, int ref, const int* others,
   bg_table* R = set->t[ref];
   if ((rc = bg_need_rows(c, set, &ref, 1, "element-of reference"))) return rc;
   Ivl o;
+  BgHold hold(c);
+  hold.own(o);
   if ((rc = bg_union_components(c, set, others, no, o))) return rc;
-  uint64_t* P = (uint64_t*)bg_alloc(c, 8 * (o.n + 1));
-  uint8_t* flag = (uint8_t*)bg_alloc(c, R->n ? R->n : 1);
-  if (!P || !flag) return BG_E_NOMEM;
+  uint64_t* P = hold.alloc<uint64_t>(o.n + 1);
+  uint8_t* flag = hold.alloc<uint8_t>(R->n ? R->n : 1);
   // the kept rows' printed lengths, summed per format tile during the compaction (no
   // formatter count pass) when the table keeps its remainders (row results print them)
-  uint16_t* blen = R->rest_len ? (uint16_t*)bg_alloc(c, 2 * (R->n ? R->n : 1)) : nullptr;
-  unsigned int* ovf = blen ? (unsigned int*)bg_alloc(c, 4) : nullptr;
-  if (blen && !ovf) return BG_E_NOMEM;
+  uint16_t* blen = R->rest_len ? hold.alloc<uint16_t>(R->n ? R->n : 1) : nullptr;
+  unsigned int* ovf = blen ? hold.alloc<unsigned int>(1) : nullptr;
+  if (!hold.ok()) return BG_E_NOMEM;
   if (ovf) BG_HIP(c, hipMemsetAsync(ovf, 0, 4, c->stream));
   if (o.n) {
     BG_LAUNCH(c, "k_lengths", k_lengths, dim3(bg_blocks(o.n, BG_NT)), dim3(BG_NT), o.s, o.e, o.n, P);
@@ -1054,8 +1050,8 @@ extern "C" int bg_element_of(bg_ctx* c, bg_set* set, int ref, const int* others,
   if ((rc = bg_scan_sum_u64(c, P, P, o.n, P + o.n))) return rc;
   if (R->n) {
     const uint64_t nblk = bg_blocks(R->n, BG_NT);
-    uint64_t* bnd = (uint64_t*)bg_alloc(c, 8 * nblk);
-    if (!bnd) return BG_E_NOMEM;
+    uint64_t* bnd = hold.alloc<uint64_t>(nblk);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_LAUNCH(c, "k_element_lo", k_element_lo, dim3(bg_blocks(nblk, BG_NT)), dim3(BG_NT), R->ks, o.e, o.n, nblk,
               bnd);
     BG_HIP(c, hipGetLastError());
@@ -1063,13 +1059,14 @@ extern "C" int bg_element_of(bg_ctx* c, bg_set* set, int ref, const int* others,
               R->ks, R->ke, R->n, o.s, o.e, o.n, P, thres, use_pct, invert, flag, set->d_name_len, R->rest_len,
               blen, ovf, (const uint64_t*)bnd);
     BG_HIP(c, hipGetLastError());
-    bg_release(c, bnd);
+    hold.drop(bnd);
   }
   uint64_t total = 0;
   uint64_t* rows = nullptr;
   uint64_t* tbytes = nullptr;
   if (!blen) {
     rc = bg_compact_flags(c, flag, R->n, &rows, &total);
+    hold(rows);
   } else {
     const unsigned nb = bg_blocks(R->n, CF_TILE);
     rc = count_scan_write(
@@ -1079,10 +1076,10 @@ extern "C" int bg_element_of(bg_ctx* c, bg_set* set, int ref, const int* others,
                     (const uint64_t*)nullptr, (uint64_t*)nullptr);
         },
         [&](uint64_t* off, uint64_t tot) -> int {
-          rows = (uint64_t*)bg_alloc(c, 8 * (tot ? tot : 1));
+          rows = hold.alloc<uint64_t>(tot ? tot : 1);
           const uint64_t nt = bg_blocks(tot, BG_FMT_TILE);
-          tbytes = (uint64_t*)bg_alloc(c, 8 * (nt ? nt : 1));
-          if (!rows || !tbytes) return BG_E_NOMEM;
+          tbytes = hold.alloc<uint64_t>(nt ? nt : 1);
+          if (!hold.ok()) return BG_E_NOMEM;
           BG_HIP(c, hipMemsetAsync(tbytes, 0, 8 * (nt ? nt : 1), c->stream));
           if (nb)
             BG_LAUNCH(c, "k_compact_rows_bytes", k_compact_rows_bytes, dim3(nb), dim3(BG_NT), flag, blen, R->n,
@@ -1094,23 +1091,18 @@ extern "C" int bg_element_of(bg_ctx* c, bg_set* set, int ref, const int* others,
     if (!rc) BG_HIP(c, hipMemcpyAsync(&h, ovf, 4, hipMemcpyDeviceToHost, c->stream));
     if (!rc) BG_HIP(c, hipStreamSynchronize(c->stream));
     if (h) {
-      bg_release(c, tbytes);
+      hold.drop(tbytes);
       tbytes = nullptr;
     }
   }
   if (rc) return rc;
-  bg_release(c, P);
-  bg_release(c, flag);
-  bg_release(c, blen);
-  bg_release(c, ovf);
-  ivl_free(c, o);
   bg_result* res = new bg_result();
   res->ctx = c;
   res->set = set;
   res->kind = RES_ROWS;
   res->n = total;
-  res->rows = rows;
-  res->tbytes = tbytes;
+  res->rows = hold.give(rows);
+  res->tbytes = hold.give(tbytes);
   res->tab = ref;
   *out = res;
   bg_mark(c, "element-of");

@@ -90,25 +90,26 @@ __global__ void k_rs_max(const uint64_t* __restrict__ K, uint64_t n, unsigned lo
 // below the highest set bit of the largest key are processed.
 int bg_sort_u64(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n) {
   if (n < 2) return 0;
-  unsigned long long* d_max = (unsigned long long*)bg_alloc(c, 8);
-  if (!d_max) return BG_E_NOMEM;
+  BgHold hold(c);
+  unsigned long long* d_max = hold.alloc<unsigned long long>(1);
+  if (!hold.ok()) return BG_E_NOMEM;
   BG_HIP(c, hipMemsetAsync(d_max, 0, 8, c->stream));
   BG_LAUNCH(c, "k_rs_max", k_rs_max, dim3(std::min<uint64_t>(bg_blocks(n, 256), 1024)), dim3(256),
             keys, n, d_max);
   BG_HIP(c, hipGetLastError());
   uint64_t mx = 0;
   int rc = bg_fetch_u64(c, (const uint64_t*)d_max, &mx);
-  bg_release(c, d_max);
+  hold.drop(d_max);
   if (rc) return rc;
   int bits = 0;
   while (bits < 64 && (mx >> bits) != 0) ++bits;
   const int passes = (bits + 7) / 8;
   if (passes == 0) return 0;
   const unsigned nt = bg_blocks(n, RS_TILE);
-  uint64_t* H = (uint64_t*)bg_alloc(c, 8ull * 256 * nt);
-  uint64_t* k2 = (uint64_t*)bg_alloc(c, 8 * n);
-  uint32_t* v2 = vals ? (uint32_t*)bg_alloc(c, 4 * n) : nullptr;
-  if (!H || !k2 || (vals && !v2)) return BG_E_NOMEM;
+  uint64_t* H = hold.alloc<uint64_t>(256ull * nt);
+  uint64_t* k2 = hold.alloc<uint64_t>(n);
+  uint32_t* v2 = vals ? hold.alloc<uint32_t>(n) : nullptr;
+  if (!hold.ok()) return BG_E_NOMEM;
   uint64_t *ka = keys, *kb = k2;
   uint32_t *va = vals, *vb = v2;
   for (int p = 0; p < passes; ++p) {
@@ -130,8 +131,5 @@ int bg_sort_u64(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n) {
     BG_HIP(c, hipMemcpyAsync(keys, ka, 8 * n, hipMemcpyDeviceToDevice, c->stream));
     if (vals) BG_HIP(c, hipMemcpyAsync(vals, va, 4 * n, hipMemcpyDeviceToDevice, c->stream));
   }
-  bg_release(c, H);
-  bg_release(c, k2);
-  bg_release(c, v2);
   return 0;
 }

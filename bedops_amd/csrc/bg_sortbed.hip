@@ -388,12 +388,13 @@ __global__ void k_sb_tput(const uint64_t* __restrict__ P, uint64_t m, const uint
 }
 static int sb_order_ties(bg_ctx* c, const uint64_t* key, const uint64_t* idx, const int64_t* endv, const uint64_t* R,
                          const uint32_t* RL, uint64_t nd, uint32_t* ord) {
-  uint64_t* tied = (uint64_t*)bg_alloc(c, 8 * (nd + 1));
-  uint64_t* start = (uint64_t*)bg_alloc(c, 8 * (nd + 1));
-  uint64_t* pos = (uint64_t*)bg_alloc(c, 8 * (nd + 1));
-  uint64_t* rid = (uint64_t*)bg_alloc(c, 8 * (nd + 1));
-  unsigned long long* more = (unsigned long long*)bg_alloc(c, 8);
-  if (!tied || !start || !pos || !rid || !more) return BG_E_NOMEM;
+  BgHold hold(c);
+  uint64_t* tied = hold.alloc<uint64_t>(nd + 1);
+  uint64_t* start = hold.alloc<uint64_t>(nd + 1);
+  uint64_t* pos = hold.alloc<uint64_t>(nd + 1);
+  uint64_t* rid = hold.alloc<uint64_t>(nd + 1);
+  unsigned long long* more = hold.alloc<unsigned long long>(1);
+  if (!hold.ok()) return BG_E_NOMEM;
   int rc = 0;
   for (uint32_t q = 0; !rc; ++q) {
     BG_HIP(c, hipMemsetAsync(more, 0, 8, c->stream));
@@ -405,12 +406,13 @@ static int sb_order_ties(bg_ctx* c, const uint64_t* key, const uint64_t* idx, co
     if ((rc = bg_fetch_u64(c, (const uint64_t*)more, &hm))) break;
     if (m == 0 || !hm) break;  // nothing tied, or every tied rest already compared in full
     if ((rc = bg_scan_sum_u64(c, start, rid, nd, nullptr))) break;  // run starts before each row
-    uint64_t* P = (uint64_t*)bg_alloc(c, 8 * m);
-    uint64_t* K = (uint64_t*)bg_alloc(c, 8 * m);
-    uint32_t* V = (uint32_t*)bg_alloc(c, 4 * m);
-    uint64_t* RID = (uint64_t*)bg_alloc(c, 8 * m);
-    uint32_t* tmp = (uint32_t*)bg_alloc(c, 4 * m);
-    if (!P || !K || !V || !RID || !tmp) rc = BG_E_NOMEM;
+    BgHold hq(c);  // this round's scratch
+    uint64_t* P = hq.alloc<uint64_t>(m);
+    uint64_t* K = hq.alloc<uint64_t>(m);
+    uint32_t* V = hq.alloc<uint32_t>(m);
+    uint64_t* RID = hq.alloc<uint64_t>(m);
+    uint32_t* tmp = hq.alloc<uint32_t>(m);
+    if (!hq.ok()) rc = BG_E_NOMEM;
     const dim3 gm(bg_blocks(m, BG_NT));
     if (!rc) {
       BG_LAUNCH(c, "k_sb_tgather", k_sb_tgather, dim3(bg_blocks(nd, BG_NT)), dim3(BG_NT), tied, pos, start, rid,
@@ -426,9 +428,7 @@ static int sb_order_ties(bg_ctx* c, const uint64_t* key, const uint64_t* idx, co
       BG_LAUNCH(c, "k_sb_tput", k_sb_tput, gm, dim3(BG_NT), P, m, tmp, ord);
       rc = bg_hip_ok(c, hipGetLastError());
     }
-    for (void* x : {(void*)P, (void*)K, (void*)V, (void*)RID, (void*)tmp}) bg_release(c, x);
   }
-  for (void* x : {(void*)tied, (void*)start, (void*)pos, (void*)rid, (void*)more}) bg_release(c, x);
   return rc;
 }
 
@@ -456,11 +456,10 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
   memset(err, 0, sizeof(*err));
   bg_bind(c);
   bg_set* set = new bg_set();
+  bg_result* r = nullptr;
+  BgHold hold(c);
+  hold.own(set, r);
   set->ctx = c;
-  auto fail = [&](int rc) {
-    bg_set_free(set);
-    return rc;
-  };
   // the texts on the device (the set owns copies of host inputs; rests point into them)
   std::vector<const char*> txt(nin);
   std::vector<uint64_t> nb(nin);
@@ -471,8 +470,8 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     if (in[f].on_device) {
       txt[f] = (const char*)in[f].data;
     } else {
-      T->own_text = (char*)bg_alloc(c, nb[f] + 64);
-      if (!T->own_text) return fail(BG_E_NOMEM);
+      T->own_text = hold.raw<char>(nb[f] + 64);
+      if (!hold.ok()) return BG_E_NOMEM;
       if (nb[f]) BG_HIP(c, hipMemcpyAsync(T->own_text, in[f].data, nb[f], hipMemcpyHostToDevice, c->stream));
       txt[f] = T->own_text;
     }
@@ -480,15 +479,15 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
   // line starts per input
   std::vector<uint64_t> L0(nin + 1, 0);
   std::vector<uint64_t*> cnts(nin, nullptr);
-  uint64_t* d_tot = (uint64_t*)bg_alloc(c, 8ull * nin);
-  if (!d_tot) return fail(BG_E_NOMEM);
+  uint64_t* d_tot = hold.alloc<uint64_t>(nin);
+  if (!hold.ok()) return BG_E_NOMEM;
   for (int f = 0; f < nin; ++f) {
     const unsigned nt = bg_blocks(nb[f], SB_TILE);
-    cnts[f] = (uint64_t*)bg_alloc(c, 8ull * (nt + 1));
-    if (!cnts[f]) return fail(BG_E_NOMEM);
+    cnts[f] = hold.alloc<uint64_t>(nt + 1);
+    if (!hold.ok()) return BG_E_NOMEM;
     if (nt) BG_LAUNCH(c, "k_sb_count", k_sb_count, dim3(nt), dim3(BG_NT), txt[f], nb[f], cnts[f]);
     int rc = bg_scan_sum_u64(c, cnts[f], cnts[f], nt, d_tot + f);
-    if (rc) return fail(rc);
+    if (rc) return rc;
   }
   std::vector<uint64_t> nnl(nin, 0);
   BG_HIP(c, hipMemcpyAsync(nnl.data(), d_tot, 8ull * nin, hipMemcpyDeviceToHost, c->stream));
@@ -496,13 +495,13 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
   for (int f = 0; f < nin; ++f) L0[f + 1] = L0[f] + (nb[f] ? nnl[f] + 1 : 0);
   const uint64_t nl = L0[nin];
   const uint64_t nl1 = nl ? nl : 1;
-  uint64_t* S = (uint64_t*)bg_alloc(c, 8 * (nl1 + 1));
-  uint64_t* Eaddr = (uint64_t*)bg_alloc(c, 8 * nl1);
-  uint32_t* F = (uint32_t*)bg_alloc(c, 4 * nl1);
-  uint64_t* dL0 = (uint64_t*)bg_alloc(c, 8ull * (nin + 1));
-  unsigned long long* first = (unsigned long long*)bg_alloc(c, 8ull * nin);
-  unsigned long long* derr = (unsigned long long*)bg_alloc(c, 16);
-  if (!S || !Eaddr || !F || !dL0 || !first || !derr) return fail(BG_E_NOMEM);
+  uint64_t* S = hold.alloc<uint64_t>(nl1 + 1);
+  uint64_t* Eaddr = hold.alloc<uint64_t>(nl1);
+  uint32_t* F = hold.alloc<uint32_t>(nl1);
+  uint64_t* dL0 = hold.alloc<uint64_t>(nin + 1);
+  unsigned long long* first = hold.alloc<unsigned long long>(nin);
+  unsigned long long* derr = hold.alloc<unsigned long long>(2);
+  if (!hold.ok()) return BG_E_NOMEM;
   for (int f = 0; f < nin; ++f) {
     const unsigned nt = bg_blocks(nb[f], SB_TILE);
     if (nt) BG_LAUNCH(c, "k_sb_starts", k_sb_starts, dim3(nt), dim3(BG_NT), txt[f], nb[f], cnts[f], S + L0[f]);
@@ -515,8 +514,8 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     BG_HIP(c, hipMemsetAsync(derr, 0xff, 16, c->stream));
     BG_HIP(c, hipStreamSynchronize(c->stream));
   }
-  uint8_t* TM = (uint8_t*)bg_alloc(c, nl1);
-  if (!TM) return fail(BG_E_NOMEM);
+  uint8_t* TM = hold.alloc<uint8_t>(nl1);
+  if (!hold.ok()) return BG_E_NOMEM;
   for (int f = 0; f < nin; ++f) {
     const uint64_t a = L0[f], b = L0[f + 1];
     if (a == b) continue;
@@ -528,16 +527,15 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
   }
   SbLines A{S, Eaddr, TM, F, dL0, nl};
   SbOut O;
-  O.flag = (uint8_t*)bg_alloc(c, nl1);
-  O.h = (uint64_t*)bg_alloc(c, 8 * nl1);
-  O.tok = (uint64_t*)bg_alloc(c, 8 * nl1);
-  O.toklen = (uint32_t*)bg_alloc(c, 4 * nl1);
-  O.start = (int64_t*)bg_alloc(c, 8 * nl1);
-  O.end = (int64_t*)bg_alloc(c, 8 * nl1);
-  O.rest = (uint64_t*)bg_alloc(c, 8 * nl1);
-  O.restlen = (uint32_t*)bg_alloc(c, 4 * nl1);
-  if (!O.flag || !O.h || !O.tok || !O.toklen || !O.start || !O.end || !O.rest || !O.restlen)
-    return fail(BG_E_NOMEM);
+  O.flag = hold.alloc<uint8_t>(nl1);
+  O.h = hold.alloc<uint64_t>(nl1);
+  O.tok = hold.alloc<uint64_t>(nl1);
+  O.toklen = hold.alloc<uint32_t>(nl1);
+  O.start = hold.alloc<int64_t>(nl1);
+  O.end = hold.alloc<int64_t>(nl1);
+  O.rest = hold.alloc<uint64_t>(nl1);
+  O.restlen = hold.alloc<uint32_t>(nl1);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (nl) {
     BG_LAUNCH(c, "k_sb_first", k_sb_first, dim3(bg_blocks(nl, BG_NT)), dim3(BG_NT), A, first);
     BG_LAUNCH(c, "k_sb_parse", k_sb_parse, dim3(bg_blocks(nl, BG_NT)), dim3(BG_NT), A, first, O, derr);
@@ -553,35 +551,37 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     err->input = f;
     err->line = li - L0[f] + 1;  // 1-based physical line of that input
     err->code = (int)(herr & 0xff);
-    return fail(bg_fail(c, BG_E_PARSE, "sort-bed: bad input line"));
+    return bg_fail(c, BG_E_PARSE, "sort-bed: bad input line");
   }
   // data lines
   uint64_t* idx = nullptr;
   uint64_t nd = 0;
   int rc = bg_compact_flags(c, O.flag, nl, &idx, &nd);
-  if (rc) return fail(rc);
+  if (rc) return rc;
+  hold(idx);
   const uint64_t nd1 = nd ? nd : 1;
   // dictionary: distinct chromosome names, ranked by strcmp on the host
-  uint64_t* key = (uint64_t*)bg_alloc(c, 8 * nd1);
-  uint32_t* val = (uint32_t*)bg_alloc(c, 4 * nd1);
-  uint8_t* uf = (uint8_t*)bg_alloc(c, nd1);
-  uint32_t* rank = (uint32_t*)bg_alloc(c, 4 * nd1);
-  if (!key || !val || !uf || !rank) return fail(BG_E_NOMEM);
+  uint64_t* key = hold.alloc<uint64_t>(nd1);
+  uint32_t* val = hold.alloc<uint32_t>(nd1);
+  uint8_t* uf = hold.alloc<uint8_t>(nd1);
+  uint32_t* rank = hold.alloc<uint32_t>(nd1);
+  if (!hold.ok()) return BG_E_NOMEM;
   std::vector<std::string> names;
   if (nd) {
     BG_LAUNCH(c, "k_sb_gather_hash", k_sb_gather_hash, dim3(bg_blocks(nd, BG_NT)), dim3(BG_NT), idx, nd,
               O.h, key, val);
-    if ((rc = bg_sort_u64(c, key, val, nd))) return fail(rc);
+    if ((rc = bg_sort_u64(c, key, val, nd))) return rc;
     BG_LAUNCH(c, "k_sb_uniq", k_sb_uniq, dim3(bg_blocks(nd, BG_NT)), dim3(BG_NT), key, nd, uf);
     uint64_t* upos = nullptr;
     uint64_t nu = 0;
-    if ((rc = bg_compact_flags(c, uf, nd, &upos, &nu))) return fail(rc);
+    if ((rc = bg_compact_flags(c, uf, nd, &upos, &nu))) return rc;
+    hold(upos);
     // ranks go into the key above bit 40 (rank << BG_KEY_SHIFT | start): as the loader
     // (bg_load.hip), at most 2^22 - 1 names keep the keys positive and distinct
-    if (nu >= (1ull << 22)) return fail(bg_fail(c, BG_E_UNSUPPORTED, "too many chromosomes"));
+    if (nu >= (1ull << 22)) return bg_fail(c, BG_E_UNSUPPORTED, "too many chromosomes");
     // representatives: hash, data-line ordinal, token address / length, then the names
-    uint64_t* rinfo = (uint64_t*)bg_alloc(c, 8 * 4 * nu);
-    if (!rinfo) return fail(BG_E_NOMEM);
+    uint64_t* rinfo = hold.alloc<uint64_t>(4 * nu);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_LAUNCH(c, "k_sb_reps", k_sb_reps, dim3(bg_blocks(nu, BG_NT)), dim3(BG_NT), upos, nu, key, val, idx,
               O.tok, O.toklen, rinfo);
     std::vector<uint64_t> hi(4 * nu);
@@ -594,9 +594,9 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
       hval[u] = (uint32_t)hi[4 * u + 1];
       noff[u + 1] = noff[u] + hi[4 * u + 3];
     }
-    char* dn = (char*)bg_alloc(c, noff[nu] + 1);
-    uint64_t* dnoff = (uint64_t*)bg_alloc(c, 8 * (nu + 1));
-    if (!dn || !dnoff) return fail(BG_E_NOMEM);
+    char* dn = hold.alloc<char>(noff[nu] + 1);
+    uint64_t* dnoff = hold.alloc<uint64_t>(nu + 1);
+    if (!hold.ok()) return BG_E_NOMEM;
     BG_HIP(c, hipMemcpyAsync(dnoff, noff.data(), 8 * (nu + 1), hipMemcpyHostToDevice, c->stream));
     BG_LAUNCH(c, "k_sb_names", k_sb_names, dim3(bg_blocks(nu, BG_NT)), dim3(BG_NT), rinfo, nu, dnoff, dn);
     std::string packed_names(noff[nu], '\0');
@@ -604,9 +604,7 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     BG_HIP(c, hipStreamSynchronize(c->stream));
     names.resize(nu);
     for (uint64_t u = 0; u < nu; ++u) names[u] = packed_names.substr(noff[u], noff[u + 1] - noff[u]);
-    bg_release(c, rinfo);
-    bg_release(c, dn);
-    bg_release(c, dnoff);
+    hold.drop(rinfo, dn, dnoff);
     std::vector<uint32_t> ord(nu);
     for (uint64_t u = 0; u < nu; ++u) ord[u] = (uint32_t)u;
     std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
@@ -617,11 +615,11 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     std::vector<std::string> sorted(nu);
     for (uint64_t r = 0; r < nu; ++r) sorted[r] = names[ord[r]];
     names = sorted;
-    uint64_t* d_uh = (uint64_t*)bg_alloc(c, 8 * nu);
-    uint32_t* d_ur = (uint32_t*)bg_alloc(c, 4 * nu);
-    uint64_t* d_rep = (uint64_t*)bg_alloc(c, 8 * nu);
-    unsigned long long* bad = (unsigned long long*)bg_alloc(c, 8);
-    if (!d_uh || !d_ur || !d_rep || !bad) return fail(BG_E_NOMEM);
+    uint64_t* d_uh = hold.alloc<uint64_t>(nu);
+    uint32_t* d_ur = hold.alloc<uint32_t>(nu);
+    uint64_t* d_rep = hold.alloc<uint64_t>(nu);
+    unsigned long long* bad = hold.alloc<unsigned long long>(1);
+    if (!hold.ok()) return BG_E_NOMEM;
     std::vector<uint64_t> rep(nu);
     for (uint64_t u = 0; u < nu; ++u) rep[u] = hval[u];
     BG_HIP(c, hipMemcpyAsync(d_uh, hh.data(), 8 * nu, hipMemcpyHostToDevice, c->stream));
@@ -633,12 +631,8 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     uint64_t hbad = 0;
     BG_HIP(c, hipMemcpyAsync(&hbad, bad, 8, hipMemcpyDeviceToHost, c->stream));
     BG_HIP(c, hipStreamSynchronize(c->stream));
-    if (hbad) return fail(bg_fail(c, BG_E_INTERNAL, "sort-bed: 64-bit chromosome hash collision"));
-    bg_release(c, d_uh);
-    bg_release(c, d_ur);
-    bg_release(c, d_rep);
-    bg_release(c, bad);
-    bg_release(c, upos);
+    if (hbad) return bg_fail(c, BG_E_INTERNAL, "sort-bed: 64-bit chromosome hash collision");
+    hold.drop(d_uh, d_ur, d_rep, bad, upos);
   }
   // the set's dictionary (names in strcmp order) for the formatter
   {
@@ -652,8 +646,8 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     }
     set->names = names;
     const size_t nbn = (packed.size() + 16) & ~(size_t)15, nbo = 4 * off.size(), blk = nbn + 2 * nbo;
-    set->d_names = (char*)bg_alloc(c, blk);
-    if (!set->d_names) return fail(BG_E_NOMEM);
+    set->d_names = hold.raw<char>(blk);
+    if (!hold.ok()) return BG_E_NOMEM;
     set->d_name_off = (uint32_t*)(set->d_names + nbn);
     set->d_name_len = (uint32_t*)(set->d_names + nbn + nbo);
     std::vector<char> h(blk, 0);
@@ -669,39 +663,32 @@ extern "C" int bg_sortbed(bg_ctx* c, int nin, const bg_input* in, bg_result** ou
     BG_LAUNCH(c, "k_sb_iota", k_sb_iota, dim3(bg_blocks(nd, BG_NT)), dim3(BG_NT), ord, nd);
     BG_LAUNCH(c, "k_sb_key", k_sb_key, dim3(bg_blocks(nd, BG_NT)), dim3(BG_NT), idx, ord, nd, O.end, rank,
               false, key);
-    if ((rc = bg_sort_u64(c, key, ord, nd))) return fail(rc);
+    if ((rc = bg_sort_u64(c, key, ord, nd))) return rc;
     BG_LAUNCH(c, "k_sb_key", k_sb_key, dim3(bg_blocks(nd, BG_NT)), dim3(BG_NT), idx, ord, nd, O.start, rank,
               true, key);
-    if ((rc = bg_sort_u64(c, key, ord, nd))) return fail(rc);
-    if ((rc = sb_order_ties(c, key, idx, O.end, O.rest, O.restlen, nd, ord))) return fail(rc);
+    if ((rc = bg_sort_u64(c, key, ord, nd))) return rc;
+    if ((rc = sb_order_ties(c, key, idx, O.end, O.rest, O.restlen, nd, ord))) return rc;
   }
-  bg_result* r = new bg_result();
+  r = new bg_result();
   r->ctx = c;
   r->set = set;
+  r->own_set = true;
+  set = nullptr;  // r's from here
   r->kind = RES_MULTI;
   r->n = nd;
   r->rest_tab = true;
-  r->s = (int64_t*)bg_alloc(c, 8 * nd1);
-  r->e = (int64_t*)bg_alloc(c, 8 * nd1);
-  r->rows = (uint64_t*)bg_alloc(c, 8 * nd1);
-  r->rlen = (uint32_t*)bg_alloc(c, 4 * nd1);
-  r->own_set = true;
-  if (!r->s || !r->e || !r->rows || !r->rlen) {
-    bg_result_free(r);
-    return BG_E_NOMEM;
-  }
+  r->s = hold.raw<int64_t>(nd1);
+  r->e = hold.raw<int64_t>(nd1);
+  r->rows = hold.raw<uint64_t>(nd1);
+  r->rlen = hold.raw<uint32_t>(nd1);
+  if (!hold.ok()) return BG_E_NOMEM;
   if (nd)
     BG_LAUNCH(c, "k_sb_emit", k_sb_emit, dim3(bg_blocks(nd, BG_NT)), dim3(BG_NT), ord, idx, rank, nd, O.start,
               O.end, O.rest, O.restlen, r->s, r->e, r->rows, r->rlen);
   BG_HIP(c, hipGetLastError());
   BG_HIP(c, hipStreamSynchronize(c->stream));
-  for (void* p : {(void*)S, (void*)Eaddr, (void*)F, (void*)dL0, (void*)first, (void*)derr, (void*)O.flag,
-                  (void*)O.h, (void*)O.tok, (void*)O.toklen, (void*)O.start, (void*)O.end, (void*)O.rest,
-                  (void*)O.restlen, (void*)idx, (void*)key, (void*)val, (void*)uf, (void*)rank, (void*)d_tot,
-                  (void*)TM})
-    bg_release(c, p);
-  for (auto p : cnts) bg_release(c, p);
   *out = r;
+  r = nullptr;  // the caller's from here
   bg_mark(c, "sort-bed");
   return 0;
 }

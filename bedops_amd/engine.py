@@ -55,7 +55,8 @@ SYMBOLS = ["bg_open", "bg_close", "bg_last_error", "bg_sync", "bg_stream", "bg_b
            "bg_device_gather_host", "bg_read_file_device", "bg_sortbed", "bg_starch_is",
            "bg_starch_decode", "bg_file_image_open", "bg_file_image_register", "bg_file_image_to_device",
            "bg_file_image_close", "bg_pwrite_device", "bg_device_release", "bg_set_output_skip", "bg_output_skip_left",
-           "bg_device_alloc", "bg_file_image_copy", "bg_copy_order", "bg_copy_fence"]
+           "bg_device_alloc", "bg_file_image_copy", "bg_copy_order", "bg_copy_fence",
+           "bg_live", "bg_fail_alloc_after"]
 UID_BYTES = 128
 
 
@@ -162,6 +163,8 @@ def load_library():
     L.bg_host_alloc.restype = vp
     L.bg_host_free.argtypes = [vp]
     L.bg_host_free.restype = None
+    L.bg_live.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.bg_fail_alloc_after.argtypes = [vp, u64]
     L.bg_prof_enable.argtypes = [vp, ctypes.c_char_p]
     L.bg_prof_read.argtypes = [vp, ctypes.c_char_p, u64]
     L.bg_result_copy_text_device.argtypes = [vp, vp, vp, u64]
@@ -547,6 +550,16 @@ class Engine:
             name, calls, ms = ln.split()
             out[name] = (int(calls), float(ms))
         return out
+
+    def live(self):
+        """(blocks, bytes) of device memory handed out by the context and not yet released"""
+        n, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.L.bg_live(self.ctx, ctypes.byref(n), ctypes.byref(b)))
+        return n.value, b.value
+
+    def fail_alloc_after(self, n):
+        """the n-th device allocation from now fails once with BG_E_NOMEM (0: disarm)"""
+        self._check(self.L.bg_fail_alloc_after(self.ctx, n))
 
     def stats(self):
         buf = ctypes.create_string_buffer(8192)

@@ -381,6 +381,15 @@ int bg_stats(const bg_ctx* ctx, char* buf, uint64_t cap);
 int bg_prof_enable(bg_ctx* ctx, const char* filter);
 int bg_prof_read(bg_ctx* ctx, char* buf, uint64_t cap);
 
+/* block accounting of the context's allocator: the number and total size of the device
+ * blocks handed out and not yet released (tables, results and text that the caller still
+ * holds included). Between calls the pair returns to its value before the call once what
+ * the call returned is freed. BG_E_HIP if releases are still waiting for the side stream */
+int bg_live(const bg_ctx* ctx, uint64_t* blocks, uint64_t* bytes);
+/* test hook: the n-th device allocation from now fails with BG_E_NOMEM ("injected" in the
+ * error text), once; n == 0 disarms */
+int bg_fail_alloc_after(bg_ctx* ctx, uint64_t n);
+
 /* pinned host buffers for input text (faster H2D); NULL on failure */
 void* bg_host_alloc(uint64_t bytes);
 void bg_host_free(void* p);
