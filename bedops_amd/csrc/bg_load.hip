@@ -2269,19 +2269,19 @@ static int strip_blank_lines(bg_ctx* c, const uint8_t* txt, uint64_t nb, char** 
   int rc = 0;
   if (nt) {
     const dim3 g(bg_blocks(nt, BG_NT / 64));
-    hipLaunchKernelGGL(k_blank_marks, g, dim3(BG_NT), 0, c->stream, txt, nb, nt, tnl, tns);
+    BG_LAUNCH(c, "k_blank_marks", k_blank_marks, g, dim3(BG_NT), txt, nb, nt, tnl, tns);
     rc = bg_hip_ok(c, hipGetLastError());
     if (!rc) rc = bg_scan_max_i64(c, tnl, xnl, nt, -1);
     if (!rc) rc = bg_scan_max_i64(c, tns, xns, nt, -2);
     if (!rc) {
-      hipLaunchKernelGGL(k_blank_pack, g, dim3(BG_NT), 0, c->stream, txt, nb, nt, (const int64_t*)xnl,
-                         (const int64_t*)xns, cnt, (const uint64_t*)nullptr, (uint8_t*)nullptr);
+      BG_LAUNCH(c, "k_blank_pack", k_blank_pack, g, dim3(BG_NT), txt, nb, nt, (const int64_t*)xnl,
+                (const int64_t*)xns, cnt, (const uint64_t*)nullptr, (uint8_t*)nullptr);
       rc = bg_hip_ok(c, hipGetLastError());
     }
     if (!rc) rc = bg_scan_sum_u64(c, cnt, cnt, nt, tot);
     if (!rc) {
-      hipLaunchKernelGGL(k_blank_pack, g, dim3(BG_NT), 0, c->stream, txt, nb, nt, (const int64_t*)xnl,
-                         (const int64_t*)xns, (uint64_t*)nullptr, (const uint64_t*)cnt, (uint8_t*)o);
+      BG_LAUNCH(c, "k_blank_pack", k_blank_pack, g, dim3(BG_NT), txt, nb, nt, (const int64_t*)xnl,
+                (const int64_t*)xns, (uint64_t*)nullptr, (const uint64_t*)cnt, (uint8_t*)o);
       rc = bg_hip_ok(c, hipGetLastError());
     }
     if (!rc) rc = bg_fetch_u64(c, tot, nout);
@@ -2602,8 +2602,9 @@ static int parse_one(bg_ctx* c, const bg_input& in, bg_table* T, LoadState& S,
     else BG_ROWV(false, false);
 #undef BG_ROWV
   } else {
-    BG_LAUNCH(c, "k_parse", k_parse, dim3(S.ntiles), dim3(BG_NT), S.txt, S.nb, T->n, S.row0, S.rlo, S.rhi, kind, R,
-              T->ks, T->ke, T->rest_off, T->rest_len, T->score, st, S.big, S.bigcap);
+    // (its own name in bg_prof_read: a test can see that a load went through the wide redo)
+    BG_LAUNCH(c, "k_parse_wide", k_parse, dim3(S.ntiles), dim3(BG_NT), S.txt, S.nb, T->n, S.row0, S.rlo, S.rhi,
+              kind, R, T->ks, T->ke, T->rest_off, T->rest_len, T->score, st, S.big, S.bigcap);
   }
   BG_HIP(c, hipGetLastError());
   BG_LAUNCH(c, "k_check_bounds", k_check_bounds, dim3(bg_blocks(S.ntiles, 256)), dim3(256), T->ks,
@@ -2893,12 +2894,17 @@ extern "C" int bg_load(bg_ctx* c, int n, const bg_input* inputs, bg_set** out) {
   const bool hst_valid = rc == 0;
   HP("rt3");
   // a BG_BED3_SET input with an error (its exact line is not known) or a staging overflow:
-  // the whole load is redone with that input's row columns (BG_BED3)
-  bool redo = false, wide = false, setredo = false;
+  // the whole load is redone with that input's row columns (BG_BED3). A blank line is no such
+  // error: when it is the first thing wrong with a set input (and nothing overflowed), the
+  // text is stripped and loaded again as a set (below); any other defect the stripped text
+  // has then takes that load to the row redo, which names the line
+  bool redo = false, wide = false, setredo = false, setblank = false;
   for (int i = 0; i < n && !rc; ++i)
     if (inputs[i].kind == BG_BED3_SET && st[i].ntiles &&
-        (hst[i].first_bad != ~0ULL || (hst[i].flags & BG_SET_OVERFLOW)))
-      redo = setredo = true;
+        (hst[i].first_bad != ~0ULL || (hst[i].flags & BG_SET_OVERFLOW))) {
+      if (!(hst[i].flags & BG_SET_OVERFLOW) && (hst[i].first_bad & 0xff) == ERR_BLANK) setblank = true;
+      else redo = setredo = true;
+    }
   // a row input with a sub-tile of more lines than k_parse_rv holds: redone with k_parse
   for (int i = 0; i < n && !rc; ++i)
     if (inputs[i].kind != BG_BED3_SET && st[i].ntiles && (hst[i].flags & BG_ROW_OVERFLOW)) redo = wide = true;
@@ -2908,6 +2914,7 @@ extern "C" int bg_load(bg_ctx* c, int n, const bg_input* inputs, bg_set** out) {
     if (inputs[i].kind != BG_BED3_SET && st[i].ntiles && hst[i].first_bad == ~0ULL && hst[i].nbig > st[i].bigcap)
       bigneed = std::max<uint64_t>(bigneed, hst[i].nbig);
   if (bigneed) redo = true;
+  if (!rc && !redo && setblank) rc = BG_E_BLANK;  // (a redo meets the blank line again)
   for (int i = 0; i < n && !rc && !redo; ++i) rc = finish_one(c, i, inputs[i], s->t[i], st[i], hst[i]);
   // blank lines (k_blank_*): the load is redone on the texts without them, which then belong
   // to the new set

@@ -26,14 +26,22 @@ def dist(c, b):
 def _half(c, b):
     cen = ((b[2]) - 1.0 + b[1]) / 2.0
     cst = float(c[1])
-    prop = 0.0 if cen < cst else (cen + 1 - cst) / float(c[2] - c[1])
-    return prop < 0.5
+    if cen < cst:
+        return True  # prop = 0
+    if c[2] == c[1]:
+        return False  # a zero-length candidate: C doubles divide to +inf, which is not below 0.5
+    return (cen + 1 - cst) / float(c[2] - c[1]) < 0.5
 
 
-def run_seq(Q, C, overlaps=True):
-    """cl_run over every ref row: returns [(left, right)] and the cache after each row"""
-    stack, fp, out, caches = [], 0, [], []
-    for b in Q:
+def run_seq(Q, C, overlaps=True, state=None, rows=None, depth=None):
+    """cl_run over the ref rows Q[rows[0]:rows[1]] (default: all) from the state (fp, cache in
+    pop order, bottom first; default: the start of the file): returns [(left, right)] and the
+    state after each row. depth, when given, is a two-entry list that is raised to the deepest
+    cache and the longest kept list seen at a row's end (what a capacity has to hold)."""
+    fp, stack = state if state is not None else (0, ())
+    stack, out, caches = list(stack), [], []
+    b0, b1 = rows if rows is not None else (0, len(Q))
+    for b in Q[b0:b1]:
         ld, rdist, left, right, lce, lc = MINUS, PLUS, -1, -1, 0, False
         kept = []
 
@@ -100,6 +108,9 @@ def run_seq(Q, C, overlaps=True):
             kept.append(left)
         if eof and right >= 0:
             kept.append(right)
+        if depth is not None:
+            depth[0] = max(depth[0], len(stack) + len(kept))
+            depth[1] = max(depth[1], len(kept))
         stack.extend(reversed(kept))
         out.append((left, right))
         caches.append((fp, tuple(stack)))
