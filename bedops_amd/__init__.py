@@ -9,7 +9,8 @@ There is no CPU fallback: if the library cannot be loaded, importing the engine
 raises.
 """
 from .engine import (BedgpuError, Engine, MAP_COUNT, MAP_MEAN, BED3, BED3_REST,  # noqa: F401
-                     BED5, lib_path)
+                     BED5, BED3_SET, RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER,
+                     lib_path)
 
-__all__ = ["Engine", "BedgpuError", "MAP_COUNT", "MAP_MEAN", "BED3", "BED3_REST", "BED5",
-           "lib_path"]
+__all__ = ["Engine", "BedgpuError", "MAP_COUNT", "MAP_MEAN", "BED3", "BED3_REST", "BED5", "BED3_SET",
+           "RESKIND_INTERVALS", "RESKIND_ROWS", "RESKIND_MAP", "RESKIND_OTHER", "lib_path"]

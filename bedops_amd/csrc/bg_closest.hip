@@ -531,6 +531,11 @@ extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_c
   }
   bg_table* Q = set->t[ref];
   bg_table* C = set->t[query];
+  {
+    int rc0 = bg_no_text(c, set, ref, "closest-features");
+    if (!rc0) rc0 = bg_no_text(c, set, query, "closest-features");
+    if (rc0) return rc0;
+  }
   if (!Q->rest_off || !C->rest_off)
     return bg_fail(c, BG_E_ARG, "closest-features needs both inputs loaded as BG_BED3_REST");
   if (C->n >= (1ull << 32))

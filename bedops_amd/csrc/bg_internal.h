@@ -138,6 +138,9 @@ struct bg_table {
   char* own_text = nullptr;  // when the library copied host text in
   uint64_t* rest_off = nullptr;
   uint32_t* rest_len = nullptr;
+  // loaded by bg_load_columns: text / rest_off / rest_len stay null, and whatever prints or
+  // compares row text refuses the table on the host, before any launch (bg_no_text)
+  bool cols = false;
   double* score = nullptr;  // BG_BED5
   bool score_int = true;     // every score is an integer (exact sums)
   bool has_zero_len = false; // some row has end == start
@@ -349,6 +352,10 @@ Ivl bg_table_ivl(bg_table* T);
 int bg_table_components(bg_ctx* c, bg_table* T, Ivl& out);
 // BG_E_ARG unless every listed table keeps its rows (not BG_BED3_SET)
 int bg_need_rows(bg_ctx* c, bg_set* set, const int* files, int nf, const char* what);
+// BG_E_ARG when table `file` came from columns (bg_table::cols): `what` needs row text
+int bg_no_text(bg_ctx* c, const bg_set* set, int file, const char* what);
+// does table M hold rows of one start whose ends do not strictly increase (bg_columns.hip)?
+int bg_cols_end_ties(bg_ctx* c, const bg_table* M, bool* any);
 // components (maximal touching-merged pieces) of one start-sorted list / of a union
 int bg_components(bg_ctx* c, const Ivl& in, Ivl& out);
 int bg_union_components(bg_ctx* c, bg_set* set, const int* files, int nf, Ivl& out);

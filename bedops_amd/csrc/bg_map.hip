@@ -1269,6 +1269,22 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
   }
   bg_table* R = set->t[ref];
   bg_table* M = set->t[map];
+  // tables loaded from columns have no text: refused here, before any launch, is whatever
+  // prints rows or ids, or orders equal rows by remainder or heap address (bg_heap.hip sizes
+  // the reference's strings from the text), and --faster (its replay does the same)
+  if (R->cols || M->cols) {
+    const int tf = R->cols ? ref : map;
+    if (opts->faster) return bg_no_text(c, set, tf, "bedmap --faster");
+    for (int k = 0; k < opts->n_ops; ++k)
+      switch (opts->ops[k]) {
+        case BG_MAP_ECHO: case BG_MAP_ECHO_MAP: case BG_MAP_ECHO_MAP_ID: case BG_MAP_ECHO_MAP_ID_UNIQ:
+        case BG_MAP_ECHO_MAP_SCORE: case BG_MAP_ECHO_MAP_SIZE: case BG_MAP_ECHO_OVERLAP_SIZE:
+        case BG_MAP_MIN_ELEMENT: case BG_MAP_MAX_ELEMENT: case BG_MAP_MIN_ELEMENT_RAND:
+        case BG_MAP_MAX_ELEMENT_RAND: case BG_MAP_WMEAN: case BG_MAP_TMEAN:
+          return bg_no_text(c, set, tf, "bedmap operation that echoes rows or orders equal rows by their text");
+        default: break;
+      }
+  }
   uint32_t need = 0;
   bool need_sum = false, need_ext = false;
   int mapfields = 3;  // map row type (bedmap/src/Input.hpp:401-418 MapFields)
@@ -1372,8 +1388,20 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
   const bool need_sq = (need & NEED_SQ) != 0;
   if (decimal && opts->shard)
     return bg_fail(c, BG_E_UNSUPPORTED, "decimal-score running sums span every chromosome: not on a chromosome shard");
+  if (decimal && M->cols) {
+    // rows from columns all have the same (empty) remainder, so map rows equal in (start, end)
+    // would be summed in heap-address order, which only the text gives: refused. The loader
+    // orders rows by start only, so equal rows need not be neighbours: rows of one start must
+    // come with strictly increasing ends (sort-bed's order, no two equal); the set order is
+    // then the coordinate order and the replay needs no text
+    bool ties = false;
+    const int rt = bg_cols_end_ties(c, M, &ties);
+    if (rt) return rt;
+    if (ties)
+      return bg_no_text(c, set, map, "non-integer scores summed over map rows of one start that are equal or not in end order");
+  }
   if (decimal) {
-    if (!M->rest_off)
+    if (!M->rest_off && !M->cols)
       return bg_fail(c, BG_E_ARG, "non-integer scores under --mean/--sum/--variance/--stdev/--cv need the map file loaded as BG_BED5_REST (equal rows are ordered by id and remainder)");
     need &= ~(NEED_SUM | NEED_SQ);
     need |= NEED_WIN;

@@ -775,6 +775,8 @@ extern "C" int bg_everything(bg_ctx* c, bg_set* set, const int* files, int nf, b
   int rc = bg_check_files(c, set, files, nf, 1);
   if (rc || !out) return rc ? rc : BG_E_ARG;
   for (int k = 0; k < nf; ++k)
+    if ((rc = bg_no_text(c, set, files[k], "--everything"))) return rc;
+  for (int k = 0; k < nf; ++k)
     if (!set->t[files[k]]->rest_off)
       return bg_fail(c, BG_E_ARG, "--everything needs every input loaded as BG_BED3_REST");
   auto load = [&](bg_table* T, Multi& m) -> int {

@@ -56,7 +56,12 @@ SYMBOLS = ["bg_open", "bg_close", "bg_last_error", "bg_sync", "bg_stream", "bg_b
            "bg_starch_decode", "bg_file_image_open", "bg_file_image_register", "bg_file_image_to_device",
            "bg_file_image_close", "bg_pwrite_device", "bg_device_release", "bg_set_output_skip", "bg_output_skip_left",
            "bg_device_alloc", "bg_file_image_copy", "bg_copy_order", "bg_copy_fence",
-           "bg_live", "bg_fail_alloc_after"]
+           "bg_live", "bg_fail_alloc_after", "bg_load_columns", "bg_set_export_rows", "bg_result_kind",
+           "bg_result_export_intervals", "bg_result_export_rows", "bg_result_export_map"]
+# what a result exports as columns (include/bedgpu.h BG_RESKIND_*)
+RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER = 0, 1, 2, 3
+# bedmap operations bg_result_export_map serves
+EXPORT_MAP_OPS = (1, 2, 3, 4, 5, 6)
 UID_BYTES = 128
 
 
@@ -88,6 +93,13 @@ class BedgpuStop(BedgpuError):
 
 class _Input(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("nbytes", ctypes.c_uint64),
+                ("on_device", ctypes.c_int), ("kind", ctypes.c_int)]
+
+
+class _Columns(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint64), ("chrom", ctypes.c_void_p), ("start", ctypes.c_void_p),
+                ("end", ctypes.c_void_p), ("score", ctypes.c_void_p),
+                ("names", ctypes.POINTER(ctypes.c_char_p)), ("nnames", ctypes.c_uint32),
                 ("on_device", ctypes.c_int), ("kind", ctypes.c_int)]
 
 
@@ -188,6 +200,12 @@ def load_library():
     L.bg_device_free.restype = None
     L.bg_device_gather_host.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(u64),
                                         ctypes.POINTER(vp), ctypes.POINTER(u64)]
+    L.bg_load_columns.argtypes = [vp, i32, ctypes.POINTER(_Columns), ctypes.POINTER(vp)]
+    L.bg_set_export_rows.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.bg_result_kind.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.bg_result_export_intervals.argtypes = [vp, vp, vp, vp, vp]
+    L.bg_result_export_rows.argtypes = [vp, vp, vp]
+    L.bg_result_export_map.argtypes = [vp, vp, i32, vp]
     _LIB = L
     return L
 
@@ -225,8 +243,9 @@ def starch_to_bed(data, chrom=None):
 
 
 class Result:
-    def __init__(self, eng, handle):
+    def __init__(self, eng, handle, map_ops=None):
         self.eng, self.h = eng, handle
+        self.map_ops = map_ops  # bedmap: the operations' BG_MAP_* codes, in order
 
     def rows(self):
         n = ctypes.c_uint64()
@@ -271,6 +290,52 @@ class Result:
                              buf.raw[:n])
         return buf.raw[:n]
 
+    def kind(self):
+        """(RESKIND_*, table): what columns() exports; table = the file whose rows a row or
+        bedmap result is about, else -1"""
+        k, t = ctypes.c_int(), ctypes.c_int()
+        self.eng._check(self.eng.L.bg_result_kind(self.h, ctypes.byref(k), ctypes.byref(t)))
+        return k.value, t.value
+
+    def columns(self, op_index=None):
+        """the result as torch tensors on the engine's device (bg_result_export_*):
+        intervals -> {"chrom", "start", "end"} (chrom indexes InputSet.chroms()); element-of ->
+        {"rows"} (indices into the reference table); bedmap -> {"values"} of operation
+        `op_index` (float64, NaN where the text has NAN), or {"values": [one per exportable
+        operation, None for the others]} when op_index is None."""
+        import torch
+        eng, L = self.eng, self.eng.L
+        kind, _ = self.kind()
+        n = self.rows()
+        dev = eng.torch_device()
+        out = {}
+        if kind == RESKIND_INTERVALS:
+            out = {"chrom": torch.empty(n, dtype=torch.int32, device=dev),
+                   "start": torch.empty(n, dtype=torch.int64, device=dev),
+                   "end": torch.empty(n, dtype=torch.int64, device=dev)}
+            eng.sync_torch()
+            eng._check(L.bg_result_export_intervals(eng.ctx, self.h, out["chrom"].data_ptr(),
+                                                    out["start"].data_ptr(), out["end"].data_ptr()))
+        elif kind == RESKIND_ROWS:
+            out = {"rows": torch.empty(n, dtype=torch.int64, device=dev)}
+            eng.sync_torch()
+            eng._check(L.bg_result_export_rows(eng.ctx, self.h, out["rows"].data_ptr()))
+        elif kind == RESKIND_MAP:
+            def one(q):
+                v = torch.empty(n, dtype=torch.float64, device=dev)
+                eng.sync_torch()
+                eng._check(L.bg_result_export_map(eng.ctx, self.h, int(q), v.data_ptr()))
+                return v
+            if op_index is not None:
+                out = {"values": one(op_index)}
+            else:
+                ops = self.map_ops or []
+                out = {"values": [one(q) if op in EXPORT_MAP_OPS else None for q, op in enumerate(ops)]}
+        else:
+            raise BedgpuError(-6, "this result has no columnar form (text only)")
+        eng.sync()
+        return out
+
     def free(self):
         if self.h:
             self.eng.L.bg_result_free(self.h)
@@ -284,8 +349,9 @@ class Result:
 
 
 class InputSet:
-    def __init__(self, eng, handle, keep):
+    def __init__(self, eng, handle, keep, kinds=None):
         self.eng, self.h, self._keep = eng, handle, keep
+        self.kinds = list(kinds) if kinds is not None else None  # the inputs' kinds as loaded
 
     def rows(self, i):
         n = ctypes.c_uint64()
@@ -299,6 +365,26 @@ class InputSet:
 
     def restrict_chrom(self, chrom):
         self.eng._check(self.eng.L.bg_set_restrict_chrom(self.eng.ctx, self.h, chrom.encode()))
+
+    def columns(self, i):
+        """table i's rows as torch tensors on the engine's device (bg_set_export_rows):
+        {"names", "chrom" (int32, index into names), "start", "end" (int64)[, "score"]}.
+        Works for text-loaded tables too; a BED3_SET table keeps no rows and raises ARG."""
+        import torch
+        eng = self.eng
+        n, dev = self.rows(i), eng.torch_device()
+        out = {"names": self.chroms(),
+               "chrom": torch.empty(n, dtype=torch.int32, device=dev),
+               "start": torch.empty(n, dtype=torch.int64, device=dev),
+               "end": torch.empty(n, dtype=torch.int64, device=dev)}
+        if self.kinds is not None and self.kinds[i] in (BED5, BED5_REST):
+            out["score"] = torch.empty(n, dtype=torch.float64, device=dev)
+        eng.sync_torch()
+        eng._check(eng.L.bg_set_export_rows(eng.ctx, self.h, i, out["chrom"].data_ptr(), out["start"].data_ptr(),
+                                            out["end"].data_ptr(),
+                                            out["score"].data_ptr() if "score" in out else None))
+        eng.sync()
+        return out
 
     def pad(self, i, lpad, rpad):
         """--range lpad:rpad applied to file i (BedPadReader.hpp:71-284)"""
@@ -322,6 +408,7 @@ class Engine:
     def __init__(self, device=0, ctx=None):
         self.L = load_library()
         self._owns = ctx is None
+        self.device = int(device)
         if ctx is not None:  # a member of a Group (the group owns the context)
             self.ctx = ctypes.c_void_p(ctx)
             return
@@ -370,7 +457,65 @@ class Engine:
             arr[i].kind = kind
         h = ctypes.c_void_p()
         self._check(self.L.bg_load(self.ctx, n, arr, ctypes.byref(h)))
-        return InputSet(self, h, keep)
+        return InputSet(self, h, keep, [k for _, k in inputs])
+
+    # -------------------------------------------------------------- columns
+    def torch_device(self):
+        import torch
+        return torch.device("cuda", self.device)
+
+    def sync_torch(self):
+        """torch's current stream on the engine's device has finished (tensors it produced may
+        be read, and tensors it allocated written, by the engine's own stream)"""
+        import torch
+        torch.cuda.current_stream(self.torch_device()).synchronize()
+
+    def load_columns(self, inputs):
+        """inputs: list of (names, chrom, start, end[, score], kind): names = this input's
+        chromosome names, chrom = per row index into names, rows sorted as sort-bed sorts
+        (names in strcmp order, then start). Columns are torch tensors (on the engine's device:
+        read in place; on the CPU: copied) or numpy arrays / sequences, converted to contiguous
+        int32 / int64 / int64 / float64. kind: BED3, BED3_SET or BED5 (BED5 takes the score)."""
+        import torch
+        n = len(inputs)
+        arr = (_Columns * n)()
+        keep = []
+        dev = self.torch_device()
+        for i, inp in enumerate(inputs):
+            names, cols, kind = inp[0], list(inp[1:-1]), inp[-1]
+            if len(cols) not in (3, 4):
+                raise BedgpuError(-6, "load_columns: (names, chrom, start, end[, score], kind)")
+            on_dev = any(isinstance(t, torch.Tensor) and t.is_cuda for t in cols)
+            conv = []
+            for t, dt in zip(cols, (torch.int32, torch.int64, torch.int64, torch.float64)):
+                t = torch.as_tensor(t)
+                if on_dev:
+                    t = t.to(device=dev, dtype=dt).contiguous()
+                    if t.data_ptr() % 16:  # a view into a larger tensor: the library wants 16-B alignment
+                        t = t.clone()
+                else:
+                    t = t.to(dtype=dt).contiguous()
+                conv.append(t)
+            if len({int(t.numel()) for t in conv}) != 1 or any(t.dim() != 1 for t in conv):
+                raise BedgpuError(-6, "load_columns: columns must be one-dimensional and of one length")
+            nm = (ctypes.c_char_p * max(len(names), 1))(*[x.encode() if isinstance(x, str) else bytes(x)
+                                                           for x in names])
+            keep += [conv, nm]
+            a = arr[i]
+            a.n = conv[0].numel()
+            a.chrom, a.start, a.end = (t.data_ptr() if a.n else None for t in conv[:3])
+            a.score = (conv[3].data_ptr() or None) if len(conv) == 4 else None
+            if len(conv) == 4 and not a.n:  # an empty score column still says "BED5"
+                z = torch.zeros(2, dtype=torch.float64, device=dev if on_dev else "cpu")
+                keep.append(z)
+                a.score = z.data_ptr()
+            a.names, a.nnames = nm, len(names)
+            a.on_device, a.kind = (1 if on_dev else 0), int(kind)
+        if any(a.on_device for a in arr):
+            self.sync_torch()
+        h = ctypes.c_void_p()
+        self._check(self.L.bg_load_columns(self.ctx, n, arr, ctypes.byref(h)))
+        return InputSet(self, h, [], [a.kind for a in arr])  # (the arrays are consumed: nothing to keep)
 
     # -------------------------------------------------------------- bedops
     def op(self, mode, s, files, spec=None, full_left=False, chop=(1, 0, False)):
@@ -481,7 +626,7 @@ class Engine:
         o.faster = 1 if faster else 0
         h = ctypes.c_void_p()
         self._check(self.L.bg_map(self.ctx, s.h, ref, map_, ctypes.byref(o), ctypes.byref(h)))
-        return Result(self, h)
+        return Result(self, h, [o.ops[k] for k in range(len(ops))])
 
     def bedmap(self, ops, ref_text, map_text=None, overlap_bp=1, precision=6, delim="|",
                skip_unmapped=False, chrom=None, criterion="bp-ovr", value=None, multidelim=";",
@@ -596,7 +741,8 @@ class Group:
         nl, nr, r0 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         self.L.bg_group_size(self.h, ctypes.byref(nl), ctypes.byref(nr), ctypes.byref(r0))
         self.nlocal, self.nranks, self.rank0 = nl.value, nr.value, r0.value
-        self.engines = [Engine(ctx=self.L.bg_group_ctx(self.h, k)) for k in range(self.nlocal)]
+        devs = list(devices) if devices is not None else [int(device)]
+        self.engines = [Engine(device=devs[k], ctx=self.L.bg_group_ctx(self.h, k)) for k in range(self.nlocal)]
 
     def gather(self, nchrom, parts):
         """parts: per local member (text_devptr, offsets[nchrom], lengths[nchrom]) over the

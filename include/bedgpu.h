@@ -339,7 +339,7 @@ int bg_group_gather(bg_group* g, int nchrom, const char* const* text, const uint
                     const uint64_t* const* len, char** out, uint64_t* out_len);
 void bg_device_free(bg_ctx* ctx, void* dptr);
 /* bg_device_free without the host wait: the block is reused only by work queued later on
- * ctx's stream (so not with a second copy stream, BEDGPU_COPY_STREAMS=2) */
+ * ctx's stream (never by the prefetch stream's copies before a bg_copy_order) */
 void bg_device_release(bg_ctx* ctx, void* dptr);
 /* host byte ranges copied back to back into one new device buffer of ctx's device (a
  * file's chromosome shard, then loaded with bg_input.on_device = 1) */
@@ -371,6 +371,66 @@ typedef struct bg_sortbed_error {
 #define BG_SB_ID_LONG 13
 #define BG_SB_ROW_LONG 14
 int bg_sortbed(bg_ctx* ctx, int n, const bg_input* inputs, bg_result** out, bg_sortbed_error* err);
+
+/* ---- columnar interface: intervals in and results out as numeric columns, no BED text ----
+ * (the reference has no counterpart: its only boundary is text)
+ *
+ * One input of bg_load_columns. Rows are sorted as sort-bed sorts them: chromosome names in
+ * strcmp order, then start. `names` is this input's own list (any order); chrom[i] indexes it. */
+typedef struct bg_columns {
+  uint64_t n;                 /* rows */
+  const int32_t* chrom;       /* per row: index into names[] */
+  const int64_t* start;
+  const int64_t* end;
+  const double*  score;       /* BG_BED5 only, else NULL */
+  const char* const* names;   /* host, NUL-terminated, this input's chromosome names */
+  uint32_t nnames;
+  int on_device;              /* 0: host arrays (copied), 1: device pointers (16-B aligned) */
+  int kind;                   /* BG_BED3, BG_BED3_SET or BG_BED5 */
+} bg_columns;
+/* N column inputs -> an ordinary set (free with bg_set_free): the dictionary is the strcmp-
+ * sorted union of every input's names, each table keyed like a text-loaded table of its kind
+ * (BG_BED3_SET: the merged set only), but without text or remainders. The arrays are consumed
+ * when the call returns (device arrays are read on ctx's stream: the caller orders its own
+ * writes before the call).
+ * Checked on the host before any launch: BG_E_ARG for a kind with remainder, a score without
+ * BG_BED5 (or BG_BED5 without one), an empty / duplicate / whitespace-holding name, and (host
+ * arrays) a chrom index outside names or, BG_E_UNSUPPORTED, a non-finite score; BG_E_CHROM
+ * for a name longer than 127 bytes. Checked on the GPU while the keys are built, first bad
+ * row first (bg_last_error names the input and the 0-based row): BG_E_RANGE for a negative
+ * coordinate, end >= 2^40 or start > end; BG_E_UNSORTED for a row whose (chromosome, start)
+ * is below its predecessor's; and for device arrays the chrom index and the score as above.
+ * (BEDGPU_COLS_BLOCKS=<n> is a test hook: it caps the key kernel's grid at n workgroups.)
+ * Operations that print row text refuse such tables with BG_E_ARG ("has no text"):
+ * bg_everything, bg_closest, bg_map with --faster or an operation that echoes rows or ids or
+ * orders equal rows by remainder or heap address, and bg_result_format of a row result.
+ * Non-integer scores under sum / mean / variance / stdev / cv need the map table's rows of one
+ * start in strictly increasing end order (no two equal), else BG_E_ARG as well. */
+int bg_load_columns(bg_ctx* ctx, int n, const bg_columns* in, bg_set** out);
+/* table `file`'s rows unkeyed into caller-owned device buffers of bg_set_rows elements, on
+ * ctx's stream (bg_sync before reading them elsewhere). chrom = index for bg_set_chrom_name.
+ * A NULL pointer skips that column. BG_E_ARG for score on a table without scores and for a
+ * BG_BED3_SET table. Works on text-loaded tables too (text -> columns). */
+int bg_set_export_rows(bg_ctx* ctx, const bg_set* set, int file, int32_t* chrom, int64_t* start,
+                       int64_t* end, double* score);
+#define BG_RESKIND_INTERVALS 0  /* merge, intersect, difference, complement, chop, partition, symmdiff */
+#define BG_RESKIND_ROWS      1  /* element-of / not-element-of: rows of table *table */
+#define BG_RESKIND_MAP       2  /* bedmap: one entry per reference row (table *table) */
+#define BG_RESKIND_OTHER     3  /* text only (everything, closest-features, sort-bed) */
+/* what a result exports (*table = -1 when it is not about one table's rows) */
+int bg_result_kind(const bg_result* res, int* kind, int* table);
+/* The export calls fill caller-owned device buffers of bg_result_rows elements on ctx's
+ * stream; a result of another kind gives BG_E_ARG. Exporting and formatting do not disturb
+ * each other, in either order.
+ * intervals: chrom (index for bg_set_chrom_name) / start / end of every output interval; a NULL
+ *   pointer skips that column.
+ * rows: the selected rows of the result's table, as indices into it, ascending.
+ * map: per reference row, the double the formatter prints for mopts.ops[op_index], NaN where it
+ *   prints NAN; BG_MAP_COUNT / INDICATOR / SUM / MEAN / MIN / MAX only (else BG_E_UNSUPPORTED);
+ *   BG_E_ARG for a result built with skip_unmapped (filter by the count instead). */
+int bg_result_export_intervals(bg_ctx* ctx, bg_result* res, int32_t* chrom, int64_t* start, int64_t* end);
+int bg_result_export_rows(bg_ctx* ctx, bg_result* res, int64_t* rows);
+int bg_result_export_map(bg_ctx* ctx, bg_result* res, int op_index, double* values);
 
 /* per-stage device timings of the last call sequence (ms), for BEDGPU_STATS */
 int bg_stats(const bg_ctx* ctx, char* buf, uint64_t cap);
