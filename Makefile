@@ -18,7 +18,7 @@ all: lib cli tools oracle
 
 lib: $(LIB)
 cli: $(CLIS)
-tools: tools/build/libbedgen.so tools/build/bedgen tools/build/heap_replay_check
+tools: tools/build/libbedgen.so tools/build/bedgen tools/build/heap_replay_check tools/build/sort_plan_check
 
 $(OBJ)/%.o: $(SRC)/%.hip $(wildcard $(SRC)/*.h) include/bedgpu.h
 	@mkdir -p $(OBJ)
@@ -65,6 +65,11 @@ tools/build/bedgen: tools/bedgen.c
 tools/build/heap_replay_check: tools/heap_replay_check.cpp $(SRC)/bg_heap_replay.h $(SRC)/bg_internal.h include/bedgpu.h
 	@mkdir -p tools/build
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -o $@ $<
+
+# the sort plan for unsorted columnar input (bg_sortplan.h, host only) printed for given widths
+tools/build/sort_plan_check: tools/sort_plan_check.cpp $(SRC)/bg_sortplan.h
+	@mkdir -p tools/build
+	$(CXX) -O2 -std=c++17 -Wall -o $@ $<
 
 oracle:
 	$(MAKE) -C oracle
