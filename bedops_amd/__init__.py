@@ -5,6 +5,9 @@ gfx950, declared in ``include/bedgpu.h``) and the drop-in C front-ends
 ``bedops_amd/bin/{bedops,bedmap}``. This package is the Python host mirror of that
 path: it binds the C ABI with ctypes and exposes the reference's operations with the
 reference's argument meaning (``bedops -m/-i/-d/-e/-n``, ``bedmap --count/--mean``).
+Intervals that are already numbers go in and out as ``torch`` tensors
+(``Engine.load_columns``, ``Engine.sort_columns`` for rows in any order,
+``InputSet.columns``, ``Result.columns``).
 There is no CPU fallback: if the library cannot be loaded, importing the engine
 raises.
 """

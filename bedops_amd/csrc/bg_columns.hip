@@ -249,8 +249,9 @@ int bg_cols_end_ties(bg_ctx* c, const bg_table* M, bool* any) {
 
 static bool name_less(const std::string& a, const std::string& b) { return strcmp(a.c_str(), b.c_str()) < 0; }
 
-// everything the host can see before any launch
-static int cols_check_args(bg_ctx* c, int n, const bg_columns* in) {
+// everything the host can see before any launch (`rows`: host arrays are walked too; the sort
+// finds a bad chrom index in its key pass on either kind of array, bg_sortcols.hip)
+int bg_cols_check_args(bg_ctx* c, int n, const bg_columns* in, bool rows) {
   for (int i = 0; i < n; ++i) {
     const bg_columns& I = in[i];
     const std::string who = "input " + std::to_string(i + 1) + ": ";
@@ -280,7 +281,7 @@ static int cols_check_args(bg_ctx* c, int n, const bg_columns* in) {
         if (I.n && ((uintptr_t)p & 15)) return bg_fail(c, BG_E_ARG, who + "device columns must be 16-byte aligned");
       continue;
     }
-    for (uint64_t r = 0; r < I.n; ++r) {
+    for (uint64_t r = 0; rows && r < I.n; ++r) {
       if ((uint32_t)I.chrom[r] >= I.nnames)
         return bg_fail(c, BG_E_ARG, who + "row " + std::to_string(r) + ": chrom index outside names");
       if (I.score && !isfinite(I.score[r]))
@@ -308,7 +309,7 @@ static int cols_report(bg_ctx* c, int file, const bg_dstatus& h) {
 // workgroups of k_cols_key: the resident grid, or fewer. BEDGPU_COLS_BLOCKS is a test hook
 // (bedgpu.h): it caps the grid so that a workgroup runs several rounds on an
 // input of a few thousand rows; read at every load so a test can set it between calls
-static uint64_t cols_grid(bg_ctx* c, const void* kern) {
+uint64_t bg_cols_grid(bg_ctx* c, const void* kern) {
   uint64_t g = bg_resident_blocks(c, kern);
   const char* s = getenv("BEDGPU_COLS_BLOCKS");
   const long v = s ? atol(s) : 0;
@@ -413,7 +414,7 @@ static int cols_load(bg_ctx* c, int n, const bg_columns* in, bg_set** out) {
       const bool lds = I.nnames <= CK_LDS_NAMES;
       const void* kern = lds ? (const void*)k_cols_key<true> : (const void*)k_cols_key<false>;
       const uint64_t nchunks = (I.n + BG_COLS_CHUNK - 1) / BG_COLS_CHUNK;
-      A.per_wg = (nchunks + cols_grid(c, kern) - 1) / cols_grid(c, kern);
+      A.per_wg = (nchunks + bg_cols_grid(c, kern) - 1) / bg_cols_grid(c, kern);
       const dim3 grid((unsigned)((nchunks + A.per_wg - 1) / A.per_wg)), block(BG_NT);
       if (lds) BG_LAUNCH(c, "k_cols_key", k_cols_key<true>, grid, block, A);
       else BG_LAUNCH(c, "k_cols_key", k_cols_key<false>, grid, block, A);
@@ -474,7 +475,7 @@ static int cols_load(bg_ctx* c, int n, const bg_columns* in, bg_set** out) {
 extern "C" int bg_load_columns(bg_ctx* c, int n, const bg_columns* in, bg_set** out) {
   if (!c || n <= 0 || !in || !out) return BG_E_ARG;
   *out = nullptr;
-  int rc = cols_check_args(c, n, in);
+  int rc = bg_cols_check_args(c, n, in, true);
   if (rc) return rc;
   rc = cols_load(c, n, in, out);
   if (rc) (void)hipStreamSynchronize(c->stream);  // queued copies may still read the caller's arrays

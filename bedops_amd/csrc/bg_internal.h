@@ -373,6 +373,13 @@ static inline bool bg_bytes_less(const char* a, uint64_t la, const char* b, uint
 }
 // stable ascending radix sort of uint64 keys with an optional uint32 payload (bg_sort.hip)
 int bg_sort_u64(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n);
+// the same by the keys' low `bits` bits only: ceil(bits / 8) digit passes, no host round trip
+int bg_sort_u64_bits(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n, int bits);
+// what the host can see of n column inputs before any launch (bg_columns.hip): kinds, scores,
+// names and alignment; `rows` adds the loader's walk over host arrays (chrom index, finite score)
+int bg_cols_check_args(bg_ctx* c, int n, const bg_columns* in, bool rows);
+// workgroups of a persistent column kernel: the resident grid, capped by BEDGPU_COLS_BLOCKS
+uint64_t bg_cols_grid(bg_ctx* c, const void* kern);
 
 // count pass -> scan -> allocate exact output -> write pass
 template <typename CountFn, typename WriteFn>

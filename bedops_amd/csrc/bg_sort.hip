@@ -3,7 +3,8 @@
 // Used off the headline path: the breakpoint/event sort of --partition and --symmdiff
 // and the re-sort of rows clamped at base 0 by --range padding (BedPadReader::getFirst,
 // applications/bed/bedops/src/BedPadReader.hpp:194-277, a std::multiset keeps ties in
-// input order, so the sort must be stable).
+// input order, so the sort must be stable). bg_sort_columns (bg_sortcols.hip) runs the digit
+// passes alone, with key widths it already knows (bg_sort_u64_bits).
 //
 // One pass per 8-bit digit over tiles of RS_TILE keys:
 //   k_rs_hist     per-tile digit histogram (LDS atomics) -> H[digit * ntiles + tile]
@@ -86,25 +87,13 @@ __global__ void k_rs_max(const uint64_t* __restrict__ K, uint64_t n, unsigned lo
   if (bg_lane() == 63) atomicMax(out, (unsigned long long)m);
 }
 
-// Sorts keys[0, n) (and vals alongside, if given) ascending, stably. Only the digits
-// below the highest set bit of the largest key are processed.
-int bg_sort_u64(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n) {
-  if (n < 2) return 0;
-  BgHold hold(c);
-  unsigned long long* d_max = hold.alloc<unsigned long long>(1);
-  if (!hold.ok()) return BG_E_NOMEM;
-  BG_HIP(c, hipMemsetAsync(d_max, 0, 8, c->stream));
-  BG_LAUNCH(c, "k_rs_max", k_rs_max, dim3(std::min<uint64_t>(bg_blocks(n, 256), 1024)), dim3(256),
-            keys, n, d_max);
-  BG_HIP(c, hipGetLastError());
-  uint64_t mx = 0;
-  int rc = bg_fetch_u64(c, (const uint64_t*)d_max, &mx);
-  hold.drop(d_max);
-  if (rc) return rc;
-  int bits = 0;
-  while (bits < 64 && (mx >> bits) != 0) ++bits;
+// Sorts keys[0, n) (and vals alongside, if given) ascending, stably, by their low `bits` bits:
+// ceil(bits / 8) digit passes and no host round trip (the caller knows its keys' width).
+int bg_sort_u64_bits(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n, int bits) {
   const int passes = (bits + 7) / 8;
-  if (passes == 0) return 0;
+  if (n < 2 || passes <= 0) return 0;
+  int rc;
+  BgHold hold(c);
   const unsigned nt = bg_blocks(n, RS_TILE);
   uint64_t* H = hold.alloc<uint64_t>(256ull * nt);
   uint64_t* k2 = hold.alloc<uint64_t>(n);
@@ -132,4 +121,24 @@ int bg_sort_u64(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n) {
     if (vals) BG_HIP(c, hipMemcpyAsync(vals, va, 4 * n, hipMemcpyDeviceToDevice, c->stream));
   }
   return 0;
+}
+
+// Sorts keys[0, n) (and vals alongside, if given) ascending, stably. Only the digits
+// below the highest set bit of the largest key are processed.
+int bg_sort_u64(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n) {
+  if (n < 2) return 0;
+  BgHold hold(c);
+  unsigned long long* d_max = hold.alloc<unsigned long long>(1);
+  if (!hold.ok()) return BG_E_NOMEM;
+  BG_HIP(c, hipMemsetAsync(d_max, 0, 8, c->stream));
+  BG_LAUNCH(c, "k_rs_max", k_rs_max, dim3(std::min<uint64_t>(bg_blocks(n, 256), 1024)), dim3(256),
+            keys, n, d_max);
+  BG_HIP(c, hipGetLastError());
+  uint64_t mx = 0;
+  int rc = bg_fetch_u64(c, (const uint64_t*)d_max, &mx);
+  hold.drop(d_max);
+  if (rc) return rc;
+  int bits = 0;
+  while (bits < 64 && (mx >> bits) != 0) ++bits;
+  return bg_sort_u64_bits(c, keys, vals, n, bits);
 }

@@ -2,7 +2,8 @@
 // §3.4) into the order bg_load_columns wants is laid out, decided on the host from three
 // numbers a key pass over the columns would reduce: the number of names, the largest start and
 // the largest end - start. Host-only and free of HIP, so tools/sort_plan_check.cpp checks it on
-// the CPU (tests/test_sort_plan.py). No kernel uses it yet: the library has no columnar sort.
+// the CPU (tests/test_sort_plan.py). bg_sort_columns (bg_sortcols.hip) reduces the three numbers
+// in its key pass and runs exactly the digit passes planned here.
 //
 // (rank, start, end) orders rows exactly as (rank, start, end - start) does, and the length is
 // the narrower number. With br = bits(nnames - 1), bs = bits(max start), bl = bits(max len):

@@ -57,7 +57,7 @@ SYMBOLS = ["bg_open", "bg_close", "bg_last_error", "bg_sync", "bg_stream", "bg_b
            "bg_file_image_close", "bg_pwrite_device", "bg_device_release", "bg_set_output_skip", "bg_output_skip_left",
            "bg_device_alloc", "bg_file_image_copy", "bg_copy_order", "bg_copy_fence",
            "bg_live", "bg_fail_alloc_after", "bg_load_columns", "bg_set_export_rows", "bg_result_kind",
-           "bg_result_export_intervals", "bg_result_export_rows", "bg_result_export_map"]
+           "bg_result_export_intervals", "bg_result_export_rows", "bg_result_export_map", "bg_sort_columns"]
 # what a result exports as columns (include/bedgpu.h BG_RESKIND_*)
 RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER = 0, 1, 2, 3
 # bedmap operations bg_result_export_map serves
@@ -206,6 +206,7 @@ def load_library():
     L.bg_result_export_intervals.argtypes = [vp, vp, vp, vp, vp]
     L.bg_result_export_rows.argtypes = [vp, vp, vp]
     L.bg_result_export_map.argtypes = [vp, vp, i32, vp]
+    L.bg_sort_columns.argtypes = [vp, ctypes.POINTER(_Columns), vp, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -352,6 +353,7 @@ class InputSet:
     def __init__(self, eng, handle, keep, kinds=None):
         self.eng, self.h, self._keep = eng, handle, keep
         self.kinds = list(kinds) if kinds is not None else None  # the inputs' kinds as loaded
+        self.order = None  # load_columns(sort=True): per input, the permutation that sorted it
 
     def rows(self, i):
         n = ctypes.c_uint64()
@@ -470,52 +472,97 @@ class Engine:
         import torch
         torch.cuda.current_stream(self.torch_device()).synchronize()
 
-    def load_columns(self, inputs):
+    def _fill_columns(self, a, names, cols, kind, keep, what):
+        """one bg_columns struct from (names, [chrom, start, end[, score]]): torch tensors (on the
+        engine's device: read in place; on the CPU: copied) or numpy arrays / sequences, converted
+        to contiguous int32 / int64 / int64 / float64; what it points to goes into `keep`"""
+        import torch
+        dev = self.torch_device()
+        on_dev = any(isinstance(t, torch.Tensor) and t.is_cuda for t in cols)
+        conv = []
+        for t, dt in zip(cols, (torch.int32, torch.int64, torch.int64, torch.float64)):
+            t = torch.as_tensor(t)
+            if on_dev:
+                t = t.to(device=dev, dtype=dt).contiguous()
+                if t.data_ptr() % 16:  # a view into a larger tensor: the library wants 16-B alignment
+                    t = t.clone()
+            else:
+                t = t.to(dtype=dt).contiguous()
+            conv.append(t)
+        if len({int(t.numel()) for t in conv}) != 1 or any(t.dim() != 1 for t in conv):
+            raise BedgpuError(-6, what + ": columns must be one-dimensional and of one length")
+        nm = (ctypes.c_char_p * max(len(names), 1))(*[x.encode() if isinstance(x, str) else bytes(x)
+                                                       for x in names])
+        keep += [conv, nm]
+        a.n = conv[0].numel()
+        a.chrom, a.start, a.end = (t.data_ptr() if a.n else None for t in conv[:3])
+        a.score = (conv[3].data_ptr() or None) if len(conv) == 4 else None
+        if len(conv) == 4 and not a.n:  # an empty score column still says "BED5"
+            z = torch.zeros(2, dtype=torch.float64, device=dev if on_dev else "cpu")
+            keep.append(z)
+            a.score = z.data_ptr()
+        a.names, a.nnames = nm, len(names)
+        a.on_device, a.kind = (1 if on_dev else 0), int(kind)
+
+    def sort_columns(self, names, chrom, start, end, score=None):
+        """one input's rows put into the order load_columns wants (bg_sort_columns): names by
+        strcmp, then start, then end, equal rows in input order. Columns as for load_columns.
+        Returns {"names", "chrom", "start", "end"[, "score"], "order"}: torch tensors on the
+        engine's device, chrom still indexing the caller's names, order[k] (int64) the input row
+        now at position k."""
+        import torch
+        cols = [chrom, start, end] + ([score] if score is not None else [])
+        arr, keep = (_Columns * 1)(), []
+        self._fill_columns(arr[0], names, cols, BED5 if score is not None else BED3, keep, "sort_columns")
+        n, dev = int(arr[0].n), self.torch_device()
+        out = {"names": list(names),
+               "chrom": torch.empty(n, dtype=torch.int32, device=dev),
+               "start": torch.empty(n, dtype=torch.int64, device=dev),
+               "end": torch.empty(n, dtype=torch.int64, device=dev)}
+        if score is not None:
+            out["score"] = torch.empty(n, dtype=torch.float64, device=dev)
+        out["order"] = torch.empty(n, dtype=torch.int64, device=dev)
+        self.sync_torch()
+        ptr = lambda k: (out[k].data_ptr() or None) if k in out else None
+        self._check(self.L.bg_sort_columns(self.ctx, arr, ptr("order"), ptr("chrom"), ptr("start"), ptr("end"),
+                                           ptr("score")))
+        self.sync()
+        return out
+
+    def load_columns(self, inputs, sort=False):
         """inputs: list of (names, chrom, start, end[, score], kind): names = this input's
         chromosome names, chrom = per row index into names, rows sorted as sort-bed sorts
         (names in strcmp order, then start). Columns are torch tensors (on the engine's device:
         read in place; on the CPU: copied) or numpy arrays / sequences, converted to contiguous
-        int32 / int64 / int64 / float64. kind: BED3, BED3_SET or BED5 (BED5 takes the score)."""
-        import torch
+        int32 / int64 / int64 / float64. kind: BED3, BED3_SET or BED5 (BED5 takes the score).
+        sort=True: rows in any order; every input goes through sort_columns first and
+        InputSet.order lists one int64 permutation tensor per input (None without sort)."""
+        order = None
+        if sort:
+            order, done = [], []
+            for inp in inputs:
+                if len(inp) not in (5, 6):
+                    raise BedgpuError(-6, "load_columns: (names, chrom, start, end[, score], kind)")
+                c = self.sort_columns(*inp[:-1])
+                order.append(c["order"])
+                done.append((c["names"], c["chrom"], c["start"], c["end"]) +
+                            ((c["score"],) if "score" in c else ()) + (inp[-1],))
+            inputs = done
         n = len(inputs)
         arr = (_Columns * n)()
         keep = []
-        dev = self.torch_device()
         for i, inp in enumerate(inputs):
             names, cols, kind = inp[0], list(inp[1:-1]), inp[-1]
             if len(cols) not in (3, 4):
                 raise BedgpuError(-6, "load_columns: (names, chrom, start, end[, score], kind)")
-            on_dev = any(isinstance(t, torch.Tensor) and t.is_cuda for t in cols)
-            conv = []
-            for t, dt in zip(cols, (torch.int32, torch.int64, torch.int64, torch.float64)):
-                t = torch.as_tensor(t)
-                if on_dev:
-                    t = t.to(device=dev, dtype=dt).contiguous()
-                    if t.data_ptr() % 16:  # a view into a larger tensor: the library wants 16-B alignment
-                        t = t.clone()
-                else:
-                    t = t.to(dtype=dt).contiguous()
-                conv.append(t)
-            if len({int(t.numel()) for t in conv}) != 1 or any(t.dim() != 1 for t in conv):
-                raise BedgpuError(-6, "load_columns: columns must be one-dimensional and of one length")
-            nm = (ctypes.c_char_p * max(len(names), 1))(*[x.encode() if isinstance(x, str) else bytes(x)
-                                                           for x in names])
-            keep += [conv, nm]
-            a = arr[i]
-            a.n = conv[0].numel()
-            a.chrom, a.start, a.end = (t.data_ptr() if a.n else None for t in conv[:3])
-            a.score = (conv[3].data_ptr() or None) if len(conv) == 4 else None
-            if len(conv) == 4 and not a.n:  # an empty score column still says "BED5"
-                z = torch.zeros(2, dtype=torch.float64, device=dev if on_dev else "cpu")
-                keep.append(z)
-                a.score = z.data_ptr()
-            a.names, a.nnames = nm, len(names)
-            a.on_device, a.kind = (1 if on_dev else 0), int(kind)
+            self._fill_columns(arr[i], names, cols, kind, keep, "load_columns")
         if any(a.on_device for a in arr):
             self.sync_torch()
         h = ctypes.c_void_p()
         self._check(self.L.bg_load_columns(self.ctx, n, arr, ctypes.byref(h)))
-        return InputSet(self, h, [], [a.kind for a in arr])  # (the arrays are consumed: nothing to keep)
+        s = InputSet(self, h, [], [a.kind for a in arr])  # (the arrays are consumed: nothing to keep)
+        s.order = order
+        return s
 
     # -------------------------------------------------------------- bedops
     def op(self, mode, s, files, spec=None, full_left=False, chop=(1, 0, False)):

@@ -407,6 +407,24 @@ typedef struct bg_columns {
  * Non-integer scores under sum / mean / variance / stdev / cv need the map table's rows of one
  * start in strictly increasing end order (no two equal), else BG_E_ARG as well. */
 int bg_load_columns(bg_ctx* ctx, int n, const bg_columns* in, bg_set** out);
+/* The columnar counterpart of bg_sortbed: one input's rows put into the order bg_load_columns
+ * accepts: chromosome names by strcmp, then start, then end; rows equal in all three keep their
+ * input order (stable). The outputs are caller-owned device buffers of in->n elements, 16-byte
+ * aligned, written by kernels on ctx's stream (bg_sync before reading them elsewhere); a NULL
+ * pointer skips that column. order[k] is the input row that lands at position k; chrom keeps the
+ * caller's own indices into in->names, so the sorted columns with the same names go straight
+ * into bg_load_columns; score is carried along for BG_BED5 (BG_E_ARG if asked for without one).
+ * `in` is host arrays (copied) or device arrays (read in place, 16-byte aligned), as above, and
+ * consumed when the call returns.
+ * Checked on the host before any launch, with the loader's codes: the kind, the score / kind
+ * match and the names as for bg_load_columns; BG_E_UNSUPPORTED for more than 2^32 - 1 rows.
+ * Checked on the GPU in the key pass, lowest bad input row first (bg_last_error names the
+ * 0-based row): BG_E_ARG for a chrom index outside names, BG_E_RANGE for a negative coordinate,
+ * end >= 2^40 or start > end. Order is the call's job and not checked; score finiteness stays
+ * the loader's check. The call makes one host round trip (the key pass's status); an input
+ * already in order is copied without any sorting pass. BEDGPU_COLS_BLOCKS caps its grids too. */
+int bg_sort_columns(bg_ctx* ctx, const bg_columns* in, int64_t* order, int32_t* chrom, int64_t* start,
+                    int64_t* end, double* score);
 /* table `file`'s rows unkeyed into caller-owned device buffers of bg_set_rows elements, on
  * ctx's stream (bg_sync before reading them elsewhere). chrom = index for bg_set_chrom_name.
  * A NULL pointer skips that column. BG_E_ARG for score on a table without scores and for a
