@@ -1284,6 +1284,7 @@ extern "C" void bg_result_free(bg_result* r) {
   bg_release(c, r->rrank);
   bg_release(c, r->wlo);
   bg_release(c, r->whi);
+  bg_release(c, r->poff);
   bg_release(c, (void*)r->lrows.idx);
   bg_release(c, (void*)r->lrows.ls);
   bg_release(c, (void*)r->lrows.coff);

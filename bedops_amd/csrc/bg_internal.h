@@ -60,6 +60,9 @@ struct LongRows {
 #define BG_FMT_MISMATCH 64ULL
 
 enum { ERR_PARSE = 1, ERR_CHROM = 2, ERR_RANGE = 3, ERR_UNSORTED = 4, ERR_BLANK = 5, ERR_SCORE = 6 };
+// bg_result_export_map_pairs: the rows from this one on wrote another number of members than
+// the offsets (the count pass) give them (bg_pairs.hip)
+enum { ERR_PAIRS = 8 };
 
 // ---------------------------------------------------------------------------------
 // host-side objects
@@ -209,6 +212,13 @@ struct bg_result {
   int map_tab = -1;          // the map table
   int mapfields = 3;         // map row type printed by --echo-map (B3Rest / B4Rest / B5Rest)
   double perc = 1.0;         // PercentOverlapMapping::perc_ of the criterion
+  // the bounds k_map_ops took every row's candidate range from (MapArgs::L / touch): the pair
+  // export derives the ranges of a result without wlo / whi from them (bg_pairs.hip)
+  int64_t win_L = 1;
+  int64_t win_touch = 0;
+  // bg_result_map_pairs: exclusive scan of cnt (n + 1 entries, the last the total); null: not run
+  uint64_t* poff = nullptr;
+  uint64_t ptotal = 0;
   bg_map_opts mopts;
   // RES_CLOSEST: per row of table `tab`, the chosen rows of table `tab2` (-1: NA)
   int64_t* left = nullptr;

@@ -1478,6 +1478,8 @@ static int map_impl(bg_ctx* c, bg_set* set, int ref, int map, const bg_map_opts*
   A.range = (int64_t)opts->range_bp;
   A.touch = tiny ? 1 : 0;
   A.perc = perc;
+  res->win_L = A.L;  // (kept for bg_result_export_map_pairs)
+  res->win_touch = A.touch;
   A.need = need;
   A.cnt = res->cnt;
   A.isum = res->isum;

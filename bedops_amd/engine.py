@@ -57,7 +57,8 @@ SYMBOLS = ["bg_open", "bg_close", "bg_last_error", "bg_sync", "bg_stream", "bg_b
            "bg_file_image_close", "bg_pwrite_device", "bg_device_release", "bg_set_output_skip", "bg_output_skip_left",
            "bg_device_alloc", "bg_file_image_copy", "bg_copy_order", "bg_copy_fence",
            "bg_live", "bg_fail_alloc_after", "bg_load_columns", "bg_set_export_rows", "bg_result_kind",
-           "bg_result_export_intervals", "bg_result_export_rows", "bg_result_export_map", "bg_sort_columns"]
+           "bg_result_export_intervals", "bg_result_export_rows", "bg_result_export_map", "bg_sort_columns",
+           "bg_result_map_pairs", "bg_result_export_map_pairs"]
 # what a result exports as columns (include/bedgpu.h BG_RESKIND_*)
 RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER = 0, 1, 2, 3
 # bedmap operations bg_result_export_map serves
@@ -207,6 +208,8 @@ def load_library():
     L.bg_result_export_rows.argtypes = [vp, vp, vp]
     L.bg_result_export_map.argtypes = [vp, vp, i32, vp]
     L.bg_sort_columns.argtypes = [vp, ctypes.POINTER(_Columns), vp, vp, vp, vp, vp]
+    L.bg_result_map_pairs.argtypes = [vp, vp, ctypes.POINTER(u64)]
+    L.bg_result_export_map_pairs.argtypes = [vp, vp, vp, vp, vp, u64]
     _LIB = L
     return L
 
@@ -334,6 +337,31 @@ class Result:
                 out = {"values": [one(q) if op in EXPORT_MAP_OPS else None for q, op in enumerate(ops)]}
         else:
             raise BedgpuError(-6, "this result has no columnar form (text only)")
+        eng.sync()
+        return out
+
+    def pairs_total(self):
+        """the number of (reference row, map row) pairs of a bedmap result (bg_result_map_pairs)"""
+        n = ctypes.c_uint64()
+        self.eng._check(self.eng.L.bg_result_map_pairs(self.eng.ctx, self.h, ctypes.byref(n)))
+        return n.value
+
+    def pairs(self, ref_rows=True):
+        """the overlap join behind a bedmap result as int64 torch tensors on the engine's device
+        (bg_result_export_map_pairs): {"offsets", "map_rows"[, "ref_rows"]}. The map rows of
+        reference row r, as indices into the map table, ascending, are
+        map_rows[offsets[r]:offsets[r + 1]]; ref_rows[k] is the reference row of pair k."""
+        import torch
+        eng = self.eng
+        total, n, dev = self.pairs_total(), self.rows(), eng.torch_device()
+        out = {"offsets": torch.empty(n + 1, dtype=torch.int64, device=dev),
+               "map_rows": torch.empty(total, dtype=torch.int64, device=dev)}
+        if ref_rows:
+            out["ref_rows"] = torch.empty(total, dtype=torch.int64, device=dev)
+        eng.sync_torch()
+        ptr = lambda k: (out[k].data_ptr() or None) if k in out else None
+        eng._check(eng.L.bg_result_export_map_pairs(eng.ctx, self.h, ptr("offsets"), ptr("ref_rows"),
+                                                    ptr("map_rows"), total))
         eng.sync()
         return out
 

@@ -449,6 +449,26 @@ int bg_result_kind(const bg_result* res, int* kind, int* table);
 int bg_result_export_intervals(bg_ctx* ctx, bg_result* res, int32_t* chrom, int64_t* start, int64_t* end);
 int bg_result_export_rows(bg_ctx* ctx, bg_result* res, int64_t* rows);
 int bg_result_export_map(bg_ctx* ctx, bg_result* res, int op_index, double* values);
+/* The overlap join behind a bedmap result: for reference row r, the rows of the map table in
+ * S(r) (the rows --echo-map* would print), as indices into the map table, ascending. That is
+ * table order, not the text route's order of equal rows by remainder or heap address, so it
+ * needs no text: it works for every bedmap result, whatever its operations, criterion and mode
+ * (two files or one, --faster, zero-length rows), on text-loaded and column-loaded tables.
+ * BG_E_ARG for a result of another kind and for one built with skip_unmapped.
+ * count: the exclusive scan of the rows' counts, 64-bit, kept by the result (freed with it,
+ *   counted by bg_live); *total = the number of pairs. One host round trip; a second call
+ *   launches nothing.
+ * export: fills caller-owned device buffers on ctx's stream, 16-byte aligned, written by kernels:
+ *   offsets (bg_result_rows + 1 elements) and ref_rows / map_rows (cap >= total elements each).
+ *   Pair k is (ref_rows[k], map_rows[k]); the pairs of row r sit at [offsets[r], offsets[r + 1]),
+ *   map_rows ascending inside a row. A NULL pointer skips that column. Runs the count itself if
+ *   the caller has not, then makes at most one more host round trip (the fill's status).
+ *   BG_E_ARG for cap < total when a pair column is asked for; BG_E_INTERNAL if the fill wrote
+ *   another number of members than the offsets give a row (nothing is written outside the
+ *   row's own slots). Exporting pairs and formatting do not disturb each other, in either order. */
+int bg_result_map_pairs(bg_ctx* ctx, bg_result* res, uint64_t* total);
+int bg_result_export_map_pairs(bg_ctx* ctx, bg_result* res, int64_t* offsets, int64_t* ref_rows,
+                               int64_t* map_rows, uint64_t cap);
 
 /* per-stage device timings of the last call sequence (ms), for BEDGPU_STATS */
 int bg_stats(const bg_ctx* ctx, char* buf, uint64_t cap);
