@@ -3,7 +3,8 @@
 //
 // In:  bg_load_columns keys (chrom index, start, end) rows into the same ks / ke columns the
 //      text loaders produce (bg_internal.h), in one pass that also applies their row checks
-//      (emit_row and the sort checks of bg_load.hip): k_cols_key.
+//      (emit_row and the sort checks of bg_load.hip): k_cols_key, built from the pieces it
+//      shares with bg_sort_columns' kernels (bg_colkern.h, whose host helpers are defined here).
 // Out: bg_set_export_rows / bg_result_export_* unkey tables and results into caller-owned
 //      device columns.
 // A column-loaded table has no text and no remainders (bg_table::cols): whatever prints or
@@ -11,16 +12,12 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "bg_internal.h"
+#include "bg_colkern.h"
 
-// consecutive rows per lane: one 16-B load of chrom, two each of start and end (and score)
+// the names tests/test_gpu_columns.py reads its shapes by: the shared values, nothing else
 #define CK_ROWS 4
-// rows a workgroup keys per round
-#define BG_COLS_CHUNK (BG_NT * CK_ROWS)
-// dictionary remap entries (local chromosome index -> global rank) kept in LDS (8 KiB)
 #define CK_LDS_NAMES 2048
-// a chrom index outside names, seen on the device (device arrays cannot be checked before)
-enum { ERR_COLS_CHROM = 7 };
+static_assert(CK_ROWS == BG_COL_ROWS && CK_LDS_NAMES == BG_COL_LDS_NAMES, "bg_colkern.h holds the values");
 
 struct ColsArgs {
   const int32_t* chrom;
@@ -35,68 +32,39 @@ struct ColsArgs {
   int64_t* ke;
   unsigned long long* runrow;  // local chromosome -> first row of its run (~0: no row)
   bg_dstatus* st;
-  uint64_t per_wg;  // consecutive chunks of BG_COLS_CHUNK rows per workgroup
+  uint64_t per_wg;  // consecutive chunks of BG_COL_CHUNK rows per workgroup
 };
 
 // One pass over the columns: 20 B read and 16 B written per row (28 and 24 with scores, which
 // are checked and copied to the table's column here: the caller's arrays may belong to another
-// HIP runtime in the process, whose pointers only kernels may touch). A
-// workgroup keys `per_wg` consecutive chunks; each lane takes CK_ROWS consecutive rows, so
-// every load and store is 16 bytes wide. The key before a lane's first row comes from the
-// lane below, the wave below through LDS, and the round before through a register of thread 0:
-// after a round's barrier it reads the last wave's key from that round's slot and keeps it.
-// The two slots alternate, so a slot is next written two rounds later, after the barrier in
-// between, which every read of it precedes. Only the first row of a workgroup's span reloads
-// its predecessor from memory.
+// HIP runtime in the process, whose pointers only kernels may touch). A workgroup keys `per_wg`
+// consecutive chunks, each lane BG_COL_ROWS consecutive rows (col_load4 / col_store4). The key
+// before a lane's first row: ColCarry; only the first row of a workgroup's span reloads its
+// predecessor from memory.
 template <bool LDSMAP>
 __global__ void __launch_bounds__(BG_NT) k_cols_key(ColsArgs A) {
-  __shared__ uint32_t smap[LDSMAP ? CK_LDS_NAMES : 1];
-  __shared__ int64_t wlast[2][BG_NT / 64];
-  if (LDSMAP) {
-    for (uint32_t k = threadIdx.x; k < A.nnames; k += BG_NT) smap[k] = A.remap[k];
-    __syncthreads();
-  }
-  const uint32_t* map = LDSMAP ? smap : A.remap;
-  const int lane = bg_lane(), w = bg_wave();
-  const uint64_t nchunks = (A.n + BG_COLS_CHUNK - 1) / BG_COLS_CHUNK;
+  __shared__ uint32_t smap[LDSMAP ? BG_COL_LDS_NAMES : 1];
+  __shared__ ColCarry<1>::Slots wlast;
+  const uint32_t* map = col_rank_map<LDSMAP>(smap, A.remap, A.nnames);
+  const int lane = bg_lane();
+  const uint64_t nchunks = (A.n + BG_COL_CHUNK - 1) / BG_COL_CHUNK;
   const uint64_t c0 = (uint64_t)blockIdx.x * A.per_wg;
   const uint64_t c1 = min(c0 + A.per_wg, nchunks);
   int64_t mlen = 0;
   bool zero = false, nonint = false;
-  uint32_t round = 0;
-  int64_t carry = LLONG_MIN;  // thread 0: the last key of the round before
-  for (uint64_t ch = c0; ch < c1; ++ch, ++round) {
-    const uint64_t i0 = ch * BG_COLS_CHUNK + (uint64_t)threadIdx.x * CK_ROWS;
-    int32_t cg[CK_ROWS];
-    int64_t s[CK_ROWS], e[CK_ROWS];
-    double sc[CK_ROWS];
-    if (i0 + CK_ROWS <= A.n) {
-      const int4 cv = *reinterpret_cast<const int4*>(A.chrom + i0);
-      const longlong2 s0 = *reinterpret_cast<const longlong2*>(A.start + i0);
-      const longlong2 s1 = *reinterpret_cast<const longlong2*>(A.start + i0 + 2);
-      const longlong2 e0 = *reinterpret_cast<const longlong2*>(A.end + i0);
-      const longlong2 e1 = *reinterpret_cast<const longlong2*>(A.end + i0 + 2);
-      cg[0] = cv.x, cg[1] = cv.y, cg[2] = cv.z, cg[3] = cv.w;
-      s[0] = s0.x, s[1] = s0.y, s[2] = s1.x, s[3] = s1.y;
-      e[0] = e0.x, e[1] = e0.y, e[2] = e1.x, e[3] = e1.y;
-      if (A.score) {
-        const double2 v0 = *reinterpret_cast<const double2*>(A.score + i0);
-        const double2 v1 = *reinterpret_cast<const double2*>(A.score + i0 + 2);
-        sc[0] = v0.x, sc[1] = v0.y, sc[2] = v1.x, sc[3] = v1.y;
-      }
-    } else {  // the input's last rows
+  ColCarry<1> carry;
+  for (uint64_t ch = c0; ch < c1; ++ch) {
+    const uint64_t i0 = ch * BG_COL_CHUNK + (uint64_t)threadIdx.x * BG_COL_ROWS;
+    int32_t cg[BG_COL_ROWS];
+    int64_t s[BG_COL_ROWS], e[BG_COL_ROWS];
+    double sc[BG_COL_ROWS];
+    col_load4(A.chrom, i0, A.n, cg);
+    col_load4(A.start, i0, A.n, s);
+    col_load4(A.end, i0, A.n, e);
+    if (A.score) col_load4(A.score, i0, A.n, sc);
+    int64_t ks[BG_COL_ROWS], ke[BG_COL_ROWS];
 #pragma unroll
-      for (int j = 0; j < CK_ROWS; ++j) {
-        const bool in = i0 + j < A.n;
-        cg[j] = in ? A.chrom[i0 + j] : 0;
-        s[j] = in ? A.start[i0 + j] : 0;
-        e[j] = in ? A.end[i0 + j] : 0;
-        sc[j] = (in && A.score) ? A.score[i0 + j] : 0.0;
-      }
-    }
-    int64_t ks[CK_ROWS], ke[CK_ROWS];
-#pragma unroll
-    for (int j = 0; j < CK_ROWS; ++j) {
+    for (int j = 0; j < BG_COL_ROWS; ++j) {
       const uint64_t i = i0 + j;
       const bool badc = (uint32_t)cg[j] >= A.nnames;
       const int64_t g = badc ? 0 : (int64_t)map[cg[j]] << BG_KEY_SHIFT;
@@ -116,27 +84,17 @@ __global__ void __launch_bounds__(BG_NT) k_cols_key(ColsArgs A) {
         }
       }
     }
-    // the key before this lane's first row
-    if (lane == 63) wlast[round & 1][w] = ks[CK_ROWS - 1];
-    int64_t pred = __shfl_up(ks[CK_ROWS - 1], 1, 64);
-    __syncthreads();
-    if (lane == 0) {
-      if (w > 0) {
-        pred = wlast[round & 1][w - 1];
-      } else if (round > 0) {
-        pred = carry;
-      } else if (i0 > 0) {  // the span's first row: its predecessor was keyed by another workgroup
-        const int32_t pc = A.chrom[i0 - 1];
-        pred = (uint32_t)pc < A.nnames
-                   ? ((int64_t)map[pc] << BG_KEY_SHIFT) | (A.start[i0 - 1] & BG_COORD_MASK)
-                   : 0;
-      } else {
-        pred = LLONG_MIN;  // row 0: no predecessor (its rank differs from every row's)
-      }
-      if (w == 0) carry = wlast[round & 1][BG_NT / 64 - 1];
+    // the key before this lane's first row (ColCarry; LLONG_MIN for row 0, whose rank then
+    // differs from every row's)
+    int64_t pk[1];
+    if (!carry.step(wlast, {ks[BG_COL_ROWS - 1]}, pk) && i0 > 0) {
+      // the span's first row: its predecessor was keyed by another workgroup
+      const int32_t pc = A.chrom[i0 - 1];
+      pk[0] = (uint32_t)pc < A.nnames ? ((int64_t)map[pc] << BG_KEY_SHIFT) | (A.start[i0 - 1] & BG_COORD_MASK) : 0;
     }
+    int64_t pred = pk[0];
 #pragma unroll
-    for (int j = 0; j < CK_ROWS; ++j) {
+    for (int j = 0; j < BG_COL_ROWS; ++j) {
       const uint64_t i = i0 + j;
       if (i < A.n) {
         // (a row with a bad chrom index has no rank: it is reported as that, not as unsorted)
@@ -147,24 +105,9 @@ __global__ void __launch_bounds__(BG_NT) k_cols_key(ColsArgs A) {
       }
       pred = ks[j];
     }
-    if (i0 + CK_ROWS <= A.n) {
-      *reinterpret_cast<longlong2*>(A.ks + i0) = make_longlong2(ks[0], ks[1]);
-      *reinterpret_cast<longlong2*>(A.ks + i0 + 2) = make_longlong2(ks[2], ks[3]);
-      *reinterpret_cast<longlong2*>(A.ke + i0) = make_longlong2(ke[0], ke[1]);
-      *reinterpret_cast<longlong2*>(A.ke + i0 + 2) = make_longlong2(ke[2], ke[3]);
-      if (A.score) {
-        *reinterpret_cast<double2*>(A.score_out + i0) = make_double2(sc[0], sc[1]);
-        *reinterpret_cast<double2*>(A.score_out + i0 + 2) = make_double2(sc[2], sc[3]);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < CK_ROWS; ++j)
-        if (i0 + j < A.n) {
-          A.ks[i0 + j] = ks[j];
-          A.ke[i0 + j] = ke[j];
-          if (A.score) A.score_out[i0 + j] = sc[j];
-        }
-    }
+    col_store4(A.ks, i0, A.n, ks);
+    col_store4(A.ke, i0, A.n, ke);
+    if (A.score) col_store4(A.score_out, i0, A.n, sc);
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) mlen = max(mlen, (int64_t)__shfl_xor(mlen, d, 64));
@@ -291,19 +234,22 @@ int bg_cols_check_args(bg_ctx* c, int n, const bg_columns* in, bool rows) {
   return 0;
 }
 
+ColRowError bg_cols_row_error(int code) {
+  switch (code) {
+    case ERR_RANGE: return {"coordinate out of range (negative, end < start or >= 2^40)", BG_E_RANGE};
+    case ERR_UNSORTED: return {"rows are not sorted (chromosome names in strcmp order, then start)", BG_E_UNSORTED};
+    case ERR_SCORE: return {"score is not finite", BG_E_UNSUPPORTED};
+    case ERR_COLS_CHROM: return {"chrom index outside names", BG_E_ARG};
+  }
+  return {"", BG_E_INTERNAL};
+}
+
 static int cols_report(bg_ctx* c, int file, const bg_dstatus& h) {
   if (h.first_bad == ~0ULL) return 0;
-  const char* what = "";
-  int rc = BG_E_INTERNAL;
-  switch ((int)(h.first_bad & 0xff)) {
-    case ERR_RANGE: what = "coordinate out of range (negative, end < start or >= 2^40)"; rc = BG_E_RANGE; break;
-    case ERR_UNSORTED: what = "rows are not sorted (chromosome names in strcmp order, then start)"; rc = BG_E_UNSORTED; break;
-    case ERR_SCORE: what = "score is not finite"; rc = BG_E_UNSUPPORTED; break;
-    case ERR_COLS_CHROM: what = "chrom index outside names"; rc = BG_E_ARG; break;
-  }
+  const ColRowError err = bg_cols_row_error((int)(h.first_bad & 0xff));
   char msg[256];
-  snprintf(msg, sizeof(msg), "input %d, row %llu: %s", file + 1, (unsigned long long)(h.first_bad >> 8), what);
-  return bg_fail(c, rc, msg);
+  snprintf(msg, sizeof(msg), "input %d, row %llu: %s", file + 1, (unsigned long long)(h.first_bad >> 8), err.what);
+  return bg_fail(c, err.rc, msg);
 }
 
 // workgroups of k_cols_key: the resident grid, or fewer. BEDGPU_COLS_BLOCKS is a test hook
@@ -315,6 +261,31 @@ uint64_t bg_cols_grid(bg_ctx* c, const void* kern) {
   const long v = s ? atol(s) : 0;
   if (v > 0 && (uint64_t)v < g) g = (uint64_t)v;
   return g;
+}
+
+unsigned bg_cols_span_grid(bg_ctx* c, const void* kern, uint64_t n, uint64_t* per_wg) {
+  const uint64_t nchunks = (n + BG_COL_CHUNK - 1) / BG_COL_CHUNK, g = bg_cols_grid(c, kern);
+  *per_wg = (nchunks + g - 1) / g;
+  return (unsigned)((nchunks + *per_wg - 1) / *per_wg);
+}
+
+unsigned bg_cols_stride_grid(bg_ctx* c, const void* kern, uint64_t n) {
+  return (unsigned)std::min<uint64_t>((n + BG_COL_CHUNK - 1) / BG_COL_CHUNK, bg_cols_grid(c, kern));
+}
+
+int bg_cols_stage(bg_ctx* c, BgHold& hold, bg_columns& I, bool score) {
+  int32_t* dc = hold.alloc<int32_t>(I.n);
+  int64_t* ds = hold.alloc<int64_t>(I.n);
+  int64_t* de = hold.alloc<int64_t>(I.n);
+  double* dv = score ? hold.alloc<double>(I.n) : nullptr;
+  if (!hold.ok()) return BG_E_NOMEM;
+  BG_HIP(c, hipMemcpyAsync(dc, I.chrom, 4 * I.n, hipMemcpyHostToDevice, c->stream));
+  BG_HIP(c, hipMemcpyAsync(ds, I.start, 8 * I.n, hipMemcpyHostToDevice, c->stream));
+  BG_HIP(c, hipMemcpyAsync(de, I.end, 8 * I.n, hipMemcpyHostToDevice, c->stream));
+  if (dv) BG_HIP(c, hipMemcpyAsync(dv, I.score, 8 * I.n, hipMemcpyHostToDevice, c->stream));
+  I.chrom = dc, I.start = ds, I.end = de;
+  if (dv) I.score = dv;
+  return 0;
 }
 
 static int cols_load(bg_ctx* c, int n, const bg_columns* in, bg_set** out) {
@@ -365,7 +336,7 @@ static int cols_load(bg_ctx* c, int n, const bg_columns* in, bg_set** out) {
   std::vector<unsigned long long*> drun((size_t)n, nullptr), hrun((size_t)n, nullptr);
   std::vector<int64_t*> sks((size_t)n, nullptr), ske((size_t)n, nullptr);  // set inputs' keyed rows
   for (int i = 0; i < n; ++i) {
-    const bg_columns& I = in[i];
+    bg_columns I = in[i];
     bg_table* T = new bg_table();
     s->t.push_back(T);
     T->kind = I.kind;
@@ -374,19 +345,13 @@ static int cols_load(bg_ctx* c, int n, const bg_columns* in, bg_set** out) {
     T->is_set = I.kind == BG_BED3_SET;
     const uint64_t n1 = I.n ? I.n : 1, m1 = I.nnames ? I.nnames : 1;
     ColsArgs A;
-    A.chrom = I.chrom, A.start = I.start, A.end = I.end, A.score = I.score;
     if (I.score) T->score = hold.raw<double>(n1);
     if (!I.on_device && I.n) {  // host arrays: staged in device temporaries (the scores in the table's column)
-      int32_t* dc = hold.alloc<int32_t>(n1);
-      int64_t* ds = hold.alloc<int64_t>(n1);
-      int64_t* de = hold.alloc<int64_t>(n1);
-      if (!hold.ok()) return BG_E_NOMEM;
-      BG_HIP(c, hipMemcpyAsync(dc, I.chrom, 4 * I.n, hipMemcpyHostToDevice, c->stream));
-      BG_HIP(c, hipMemcpyAsync(ds, I.start, 8 * I.n, hipMemcpyHostToDevice, c->stream));
-      BG_HIP(c, hipMemcpyAsync(de, I.end, 8 * I.n, hipMemcpyHostToDevice, c->stream));
-      A.chrom = dc, A.start = ds, A.end = de;
+      const int rc = bg_cols_stage(c, hold, I, false);
+      if (rc) return rc;
     }
     if (!hold.ok()) return BG_E_NOMEM;
+    A.chrom = I.chrom, A.start = I.start, A.end = I.end, A.score = I.score;
     A.score_out = T->score;
     if (I.score && I.n && !I.on_device) {  // (in place: the kernel's copy onto itself changes nothing)
       BG_HIP(c, hipMemcpyAsync(T->score, I.score, 8 * I.n, hipMemcpyHostToDevice, c->stream));
@@ -411,14 +376,8 @@ static int cols_load(bg_ctx* c, int n, const bg_columns* in, bg_set** out) {
       A.ks = ks, A.ke = ke;
       A.runrow = drun[i];
       A.st = dst + i;
-      const bool lds = I.nnames <= CK_LDS_NAMES;
-      const void* kern = lds ? (const void*)k_cols_key<true> : (const void*)k_cols_key<false>;
-      const uint64_t nchunks = (I.n + BG_COLS_CHUNK - 1) / BG_COLS_CHUNK;
-      A.per_wg = (nchunks + bg_cols_grid(c, kern) - 1) / bg_cols_grid(c, kern);
-      const dim3 grid((unsigned)((nchunks + A.per_wg - 1) / A.per_wg)), block(BG_NT);
-      if (lds) BG_LAUNCH(c, "k_cols_key", k_cols_key<true>, grid, block, A);
-      else BG_LAUNCH(c, "k_cols_key", k_cols_key<false>, grid, block, A);
-      BG_HIP(c, hipGetLastError());
+      BG_COL_LAUNCH(c, "k_cols_key", k_cols_key, I.nnames <= BG_COL_LDS_NAMES,
+                    bg_cols_span_grid(c, kern, I.n, &A.per_wg), A);
     }
     if (T->is_set) sks[i] = ks, ske[i] = ke;
   }

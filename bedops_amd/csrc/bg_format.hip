@@ -998,11 +998,13 @@ __global__ void __launch_bounds__(BG_NT) k_fmt_count(FmtArgs A, uint64_t* __rest
 #endif
 #if BG_FMT_UNROLL
 #define FMT_UNROLL _Pragma("unroll")
-// (RES_MAP's render is too large to unroll; its loops stay rolled)
-#pragma clang diagnostic ignored "-Wpass-failed"
 #else
 #define FMT_UNROLL
 #endif
+// (RES_MAP's render is too large to unroll; its loops stay rolled: the failed-unroll warning is
+// silenced for this kernel only)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"
 template <int KIND>
 __global__ void __launch_bounds__(BG_NT) k_fmt_write(FmtArgs A, const uint64_t* __restrict__ toff,
                                                      char* __restrict__ out) {
@@ -1069,6 +1071,7 @@ FMT_UNROLL
   for (uint64_t p = al0 + 16ull * threadIdx.x; p < al1; p += 16ull * BG_NT)
     *reinterpret_cast<uint4*>(out + p) = *reinterpret_cast<const uint4*>(bb + (p - a0));
 }
+#pragma clang diagnostic pop
 
 // RES_IVL rows ("%s\t%lu\t%lu\n"): thread t renders rows 2t and 2t+1 of the tile, both
 // loaded up front as 16-byte pairs, so one block scan of the per-thread byte counts places

@@ -60,6 +60,9 @@ struct LongRows {
 #define BG_FMT_MISMATCH 64ULL
 
 enum { ERR_PARSE = 1, ERR_CHROM = 2, ERR_RANGE = 3, ERR_UNSORTED = 4, ERR_BLANK = 5, ERR_SCORE = 6 };
+// bg_load_columns, bg_sort_columns: a chrom index outside names, seen on the device (device
+// arrays cannot be checked before)
+enum { ERR_COLS_CHROM = 7 };
 // bg_result_export_map_pairs: the rows from this one on wrote another number of members than
 // the offsets (the count pass) give them (bg_pairs.hip)
 enum { ERR_PAIRS = 8 };
@@ -786,8 +789,12 @@ __device__ __forceinline__ int bg_frest_cmp(const char* text, const uint64_t* re
   return la == lb ? 0 : (la < lb ? -1 : 1);
 }
 
+// (the first_bad word of a bg_dstatus, or of another status struct that keeps one)
+__device__ __forceinline__ void bg_report(unsigned long long* first_bad, uint64_t row, int code) {
+  atomicMin(first_bad, (unsigned long long)((row << 8) | (uint64_t)code));
+}
 __device__ __forceinline__ void bg_report(bg_dstatus* st, uint64_t row, int code) {
-  atomicMin(&st->first_bad, (unsigned long long)((row << 8) | (uint64_t)code));
+  bg_report(&st->first_bad, row, code);
 }
 
 // bg_heap.hip: the reference's heap address of every map row (device array), and whether
