@@ -7,13 +7,15 @@ path: it binds the C ABI with ctypes and exposes the reference's operations with
 reference's argument meaning (``bedops -m/-i/-d/-e/-n``, ``bedmap --count/--mean``).
 Intervals that are already numbers go in and out as ``torch`` tensors
 (``Engine.load_columns``, ``Engine.sort_columns`` for rows in any order,
-``InputSet.columns``, ``Result.columns``).
+``InputSet.columns``, ``Result.columns``; closest-features on such tables:
+``Engine.closest_rows``, ``Result.closest``).
 There is no CPU fallback: if the library cannot be loaded, importing the engine
 raises.
 """
 from .engine import (BedgpuError, Engine, MAP_COUNT, MAP_MEAN, BED3, BED3_REST,  # noqa: F401
                      BED5, BED3_SET, RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER,
-                     lib_path)
+                     RESKIND_CLOSEST, DIST_NA, lib_path)
 
 __all__ = ["Engine", "BedgpuError", "MAP_COUNT", "MAP_MEAN", "BED3", "BED3_REST", "BED5", "BED3_SET",
-           "RESKIND_INTERVALS", "RESKIND_ROWS", "RESKIND_MAP", "RESKIND_OTHER", "lib_path"]
+           "RESKIND_INTERVALS", "RESKIND_ROWS", "RESKIND_MAP", "RESKIND_OTHER", "RESKIND_CLOSEST",
+           "DIST_NA", "lib_path"]

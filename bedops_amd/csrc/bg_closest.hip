@@ -518,26 +518,13 @@ static int closest_pass(bg_ctx* c, ClArgs& A, bool* ovf) {
   return rc;
 }
 
-extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_closest_opts* o,
-                          bg_result** out) {
-  if (!c || !set || !o || !out || ref < 0 || query < 0 || ref >= (int)set->t.size() ||
-      query >= (int)set->t.size())
-    return BG_E_ARG;
-  *out = nullptr;
-  {
-    const int f[2] = {ref, query};
-    int rc0 = bg_need_rows(c, set, f, 2, "closest-features");
-    if (rc0) return rc0;
-  }
+// The scan behind bg_closest and bg_closest_rows, on two tables that keep their rows: it reads
+// their keyed columns and the query table's maxlen only, so text-loaded and column-loaded tables
+// are the same to it. `crows`: the result is bg_closest_rows' (bg_result::crows).
+static int closest_scan(bg_ctx* c, bg_set* set, int ref, int query, const bg_closest_opts* o, bool crows,
+                        bg_result** out) {
   bg_table* Q = set->t[ref];
   bg_table* C = set->t[query];
-  {
-    int rc0 = bg_no_text(c, set, ref, "closest-features");
-    if (!rc0) rc0 = bg_no_text(c, set, query, "closest-features");
-    if (rc0) return rc0;
-  }
-  if (!Q->rest_off || !C->rest_off)
-    return bg_fail(c, BG_E_ARG, "closest-features needs both inputs loaded as BG_BED3_REST");
   if (C->n >= (1ull << 32))
     return bg_fail(c, BG_E_UNSUPPORTED, "more than 2^32 rows in <query-file>");
   bg_result* r = new bg_result();
@@ -546,6 +533,7 @@ extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_c
   r->ctx = c;
   r->set = set;
   r->kind = RES_CLOSEST;
+  r->crows = crows;
   r->tab = ref;
   r->tab2 = query;
   r->copts = *o;
@@ -582,4 +570,36 @@ extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_c
   *out = r;
   r = nullptr;  // the caller's from here
   return 0;
+}
+
+// what both entry points check first: the handles, the table indices, and that both tables kept
+// their rows (not BG_BED3_SET)
+static int closest_tables(bg_ctx* c, bg_set* set, int ref, int query, bg_result** out) {
+  if (!c || !set || !out || ref < 0 || query < 0 || ref >= (int)set->t.size() || query >= (int)set->t.size())
+    return BG_E_ARG;
+  *out = nullptr;
+  const int f[2] = {ref, query};
+  return bg_need_rows(c, set, f, 2, "closest-features");
+}
+
+extern "C" int bg_closest(bg_ctx* c, bg_set* set, int ref, int query, const bg_closest_opts* o,
+                          bg_result** out) {
+  if (!o) return BG_E_ARG;
+  int rc = closest_tables(c, set, ref, query, out);
+  if (rc) return rc;
+  if ((rc = bg_no_text(c, set, ref, "closest-features"))) return rc;
+  if ((rc = bg_no_text(c, set, query, "closest-features"))) return rc;
+  if (!set->t[ref]->rest_off || !set->t[query]->rest_off)
+    return bg_fail(c, BG_E_ARG, "closest-features needs both inputs loaded as BG_BED3_REST");
+  return closest_scan(c, set, ref, query, o, false, out);
+}
+
+extern "C" int bg_closest_rows(bg_ctx* c, bg_set* set, int ref, int query, int no_overlaps, bg_result** out) {
+  const int rc = closest_tables(c, set, ref, query, out);
+  if (rc) return rc;
+  bg_closest_opts o;  // the print options of a bare `closest-features <input-file> <query-file>`
+  memset(&o, 0, sizeof(o));
+  o.no_overlaps = no_overlaps ? 1 : 0;
+  o.delim[0] = '|';
+  return closest_scan(c, set, ref, query, &o, true, out);
 }

@@ -467,6 +467,10 @@ extern "C" int bg_result_kind(const bg_result* r, int* kind, int* table) {
     case RES_IVL: *kind = BG_RESKIND_INTERVALS; break;
     case RES_ROWS: *kind = BG_RESKIND_ROWS; t = r->tab; break;
     case RES_MAP: *kind = BG_RESKIND_MAP; t = r->tab; break;
+    case RES_CLOSEST:  // (bg_closest's own results stay "text only", as before bg_closest_rows)
+      if (r->crows) { *kind = BG_RESKIND_CLOSEST; t = r->tab; }
+      else *kind = BG_RESKIND_OTHER;
+      break;
     default: *kind = BG_RESKIND_OTHER; break;
   }
   if (table) *table = t;

@@ -1467,6 +1467,11 @@ extern "C" int bg_result_format(bg_ctx* c, bg_result* r, uint64_t* nbytes) {
   if (!c || !r) return BG_E_ARG;
   if (r->kind == RES_ROWS && !r->set->t[r->tab]->rest_off)
     return bg_fail(c, BG_E_ARG, "row result needs its table loaded as BG_BED3_REST");
+  if (r->kind == RES_CLOSEST)  // (bg_closest_rows takes tables without remainders: columns only)
+    for (const int t : {r->tab, r->tab2})
+      if (!r->set->t[t]->rest_off)
+        return bg_fail(c, BG_E_ARG, "closest-features: input " + std::to_string(t + 1) +
+                                        " has no text to print (loaded from columns or without its remainder)");
   if (r->formatted) {
     if (nbytes) *nbytes = r->nbytes;
     return r->stopped ? bg_fail(c, BG_E_VISITOR, "Unable to process a 'NAN' with PrintAllScorePrecision.") : 0;

@@ -66,6 +66,9 @@ enum { ERR_COLS_CHROM = 7 };
 // bg_result_export_map_pairs: the rows from this one on wrote another number of members than
 // the offsets (the count pass) give them (bg_pairs.hip)
 enum { ERR_PAIRS = 8 };
+// bg_result_export_closest: a chosen row outside [-1, rows of the query table), or on another
+// chromosome than its reference row (bg_closest_export.hip)
+enum { ERR_CLOSEST = 9 };
 
 // ---------------------------------------------------------------------------------
 // host-side objects
@@ -228,6 +231,7 @@ struct bg_result {
   int64_t* right = nullptr;
   int tab2 = -1;
   bg_closest_opts copts;
+  bool crows = false;  // built by bg_closest_rows: BG_RESKIND_CLOSEST (the tables may have no text)
   // rendered text
   char* text = nullptr;
   uint64_t nbytes = 0;

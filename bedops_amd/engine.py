@@ -58,9 +58,11 @@ SYMBOLS = ["bg_open", "bg_close", "bg_last_error", "bg_sync", "bg_stream", "bg_b
            "bg_device_alloc", "bg_file_image_copy", "bg_copy_order", "bg_copy_fence",
            "bg_live", "bg_fail_alloc_after", "bg_load_columns", "bg_set_export_rows", "bg_result_kind",
            "bg_result_export_intervals", "bg_result_export_rows", "bg_result_export_map", "bg_sort_columns",
-           "bg_result_map_pairs", "bg_result_export_map_pairs"]
+           "bg_result_map_pairs", "bg_result_export_map_pairs", "bg_closest_rows", "bg_result_export_closest"]
 # what a result exports as columns (include/bedgpu.h BG_RESKIND_*)
-RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER = 0, 1, 2, 3
+RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER, RESKIND_CLOSEST = 0, 1, 2, 3, 4
+# the distance of a row that has no element on that side (include/bedgpu.h BG_DIST_NA)
+DIST_NA = -(1 << 63)
 # bedmap operations bg_result_export_map serves
 EXPORT_MAP_OPS = (1, 2, 3, 4, 5, 6)
 UID_BYTES = 128
@@ -210,6 +212,8 @@ def load_library():
     L.bg_sort_columns.argtypes = [vp, ctypes.POINTER(_Columns), vp, vp, vp, vp, vp]
     L.bg_result_map_pairs.argtypes = [vp, vp, ctypes.POINTER(u64)]
     L.bg_result_export_map_pairs.argtypes = [vp, vp, vp, vp, vp, u64]
+    L.bg_closest_rows.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(vp)]
+    L.bg_result_export_closest.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -306,7 +310,7 @@ class Result:
         intervals -> {"chrom", "start", "end"} (chrom indexes InputSet.chroms()); element-of ->
         {"rows"} (indices into the reference table); bedmap -> {"values"} of operation
         `op_index` (float64, NaN where the text has NAN), or {"values": [one per exportable
-        operation, None for the others]} when op_index is None."""
+        operation, None for the others]} when op_index is None; closest_rows -> closest()."""
         import torch
         eng, L = self.eng, self.eng.L
         kind, _ = self.kind()
@@ -335,8 +339,28 @@ class Result:
             else:
                 ops = self.map_ops or []
                 out = {"values": [one(q) if op in EXPORT_MAP_OPS else None for q, op in enumerate(ops)]}
+        elif kind == RESKIND_CLOSEST:
+            return self.closest()
         else:
             raise BedgpuError(-6, "this result has no columnar form (text only)")
+        eng.sync()
+        return out
+
+    def closest(self, shortest=False):
+        """a closest-features result (closest_rows or closest_op) as int64 torch tensors on the
+        engine's device (bg_result_export_closest), one entry per reference row:
+        {"left", "right", "left_dist", "right_dist"}: the query-table rows printed on the left and
+        on the right (-1 where the text has NA) and what --dist prints for them (DIST_NA there);
+        shortest=True: {"rows", "dist"}, the one element and distance --shortest --dist prints."""
+        import torch
+        eng = self.eng
+        n, dev = self.rows(), eng.torch_device()
+        keys = ("rows", "dist") if shortest else ("left", "right", "left_dist", "right_dist")
+        out = {k: torch.empty(n, dtype=torch.int64, device=dev) for k in keys}
+        eng.sync_torch()
+        ptr = lambda k: (out[k].data_ptr() or None) if k in out else None
+        eng._check(eng.L.bg_result_export_closest(eng.ctx, self.h, ptr("left"), ptr("right"), ptr("left_dist"),
+                                                  ptr("right_dist"), ptr("rows"), ptr("dist")))
         eng.sync()
         return out
 
@@ -741,6 +765,13 @@ class Engine:
         o.delim = delim.encode()
         h = ctypes.c_void_p()
         self._check(self.L.bg_closest(self.ctx, s.h, ref, query, ctypes.byref(o), ctypes.byref(h)))
+        return Result(self, h)
+
+    def closest_rows(self, s, ref=0, query=1, no_overlaps=False):
+        """the closest-features scan on any two tables of `s` that keep their rows, text-loaded
+        or from load_columns (bg_closest_rows) -> Result, read with Result.closest()"""
+        h = ctypes.c_void_p()
+        self._check(self.L.bg_closest_rows(self.ctx, s.h, ref, query, int(bool(no_overlaps)), ctypes.byref(h)))
         return Result(self, h)
 
     def closest(self, input_text, query_text, shortest=False, dist=False, no_ref=False,

@@ -224,6 +224,14 @@ int bg_map(bg_ctx* ctx, bg_set* set, int ref, int map, const bg_map_opts* opts,
  * the <query-file> table, both loaded as BG_BED3_REST; one output line per ref row */
 int bg_closest(bg_ctx* ctx, bg_set* set, int ref, int query, const bg_closest_opts* opts,
                bg_result** out);
+/* The same scan for callers that want columns, not text: `ref` and `query` are any two tables
+ * that keep their rows (BG_BED3, BG_BED3_REST, BG_BED5, BG_BED5_REST; text-loaded or loaded by
+ * bg_load_columns), BG_E_ARG for a BG_BED3_SET table; the limit of 2^32 query rows is
+ * bg_closest's. The result carries the print options of a bare `closest-features` run
+ * (no_overlaps as given) and is read with bg_result_export_closest; bg_result_format /
+ * bg_result_write work on it when both tables have remainders and else return BG_E_ARG
+ * ("has no text") before any launch. */
+int bg_closest_rows(bg_ctx* ctx, bg_set* set, int ref, int query, int no_overlaps, bg_result** out);
 
 /* results */
 int bg_result_rows(const bg_result* res, uint64_t* rows);
@@ -434,7 +442,8 @@ int bg_set_export_rows(bg_ctx* ctx, const bg_set* set, int file, int32_t* chrom,
 #define BG_RESKIND_INTERVALS 0  /* merge, intersect, difference, complement, chop, partition, symmdiff */
 #define BG_RESKIND_ROWS      1  /* element-of / not-element-of: rows of table *table */
 #define BG_RESKIND_MAP       2  /* bedmap: one entry per reference row (table *table) */
-#define BG_RESKIND_OTHER     3  /* text only (everything, closest-features, sort-bed) */
+#define BG_RESKIND_OTHER     3  /* text only (everything, bg_closest, sort-bed) */
+#define BG_RESKIND_CLOSEST   4  /* bg_closest_rows: one entry per reference row (table *table) */
 /* what a result exports (*table = -1 when it is not about one table's rows) */
 int bg_result_kind(const bg_result* res, int* kind, int* table);
 /* The export calls fill caller-owned device buffers of bg_result_rows elements on ctx's
@@ -469,6 +478,26 @@ int bg_result_export_map(bg_ctx* ctx, bg_result* res, int op_index, double* valu
 int bg_result_map_pairs(bg_ctx* ctx, bg_result* res, uint64_t* total);
 int bg_result_export_map_pairs(bg_ctx* ctx, bg_result* res, int64_t* offsets, int64_t* ref_rows,
                                int64_t* map_rows, uint64_t cap);
+/* A closest-features result (of bg_closest_rows or of bg_closest) as columns: caller-owned
+ * device buffers of bg_result_rows elements, 16-byte aligned, written by one kernel on ctx's
+ * stream; a NULL pointer skips that column (all NULL: no launch). Per reference row:
+ *   left_rows / right_rows   the query-table row printed on the left / right, -1 where the text
+ *                            has NA;
+ *   left_dist / right_dist   what --dist prints for it (getDistance, ClosestFeature.cpp:244-255:
+ *                            <= 0 on the left, >= 0 on the right), BG_DIST_NA where the row is -1;
+ *   shortest_rows / _dist    the one element and distance --shortest --dist prints (PrintShortest,
+ *                            Printers.hpp:112-200: an overlapping left, then an overlapping right,
+ *                            with distance 0; else the smaller absolute distance, ties to the
+ *                            left), -1 / BG_DIST_NA when there is neither. The print options the
+ *                            result was built with play no part.
+ * BG_E_ARG for a result of another kind. One host round trip (the kernel's status):
+ * BG_E_INTERNAL if a chosen row lies outside the query table or on another chromosome than its
+ * reference row (such a row is not read). Exporting and formatting do not disturb each other, in
+ * either order. BEDGPU_COLS_BLOCKS caps the kernel's grid. */
+#define BG_DIST_NA INT64_MIN
+int bg_result_export_closest(bg_ctx* ctx, bg_result* res, int64_t* left_rows, int64_t* right_rows,
+                             int64_t* left_dist, int64_t* right_dist, int64_t* shortest_rows,
+                             int64_t* shortest_dist);
 
 /* per-stage device timings of the last call sequence (ms), for BEDGPU_STATS */
 int bg_stats(const bg_ctx* ctx, char* buf, uint64_t cap);
