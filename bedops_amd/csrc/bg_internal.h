@@ -395,6 +395,12 @@ int bg_sort_u64_bits(bg_ctx* c, uint64_t* keys, uint32_t* vals, uint64_t n, int 
 // what the host can see of n column inputs before any launch (bg_columns.hip): kinds, scores,
 // names and alignment; `rows` adds the loader's walk over host arrays (chrom index, finite score)
 int bg_cols_check_args(bg_ctx* c, int n, const bg_columns* in, bool rows);
+// the pair fill of a bedmap result (bg_pairs.hip) writing, instead of indices, every member's
+// score at its pair's slot: row r's scores at vals[poff[r] .. poff[r + 1]), in map-row order.
+// r->poff is there and r->ptotal > 0 (bg_result_map_pairs); one launch and no host round trip.
+// bg_pairs_status then fetches the fill's status (one round trip): BG_E_INTERNAL for ERR_PAIRS
+int bg_pairs_scores(bg_ctx* c, bg_result* r, double* vals);
+int bg_pairs_status(bg_ctx* c);
 // workgroups of a persistent column kernel: the resident grid, capped by BEDGPU_COLS_BLOCKS
 uint64_t bg_cols_grid(bg_ctx* c, const void* kern);
 

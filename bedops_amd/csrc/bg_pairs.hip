@@ -11,6 +11,8 @@
 //                 are contiguous (thread-per-row stores at offsets[r] + j scatter every one).
 //   k_pairs_rows  long rows by class: one thread per reference row merges the class ranges in
 //                 index order, as bg_map_cands does for the formatter's --echo-map walk.
+// Either writes, besides or instead of the indices, the member's score at the pair's slot
+// (bg_pairs_scores: the segments bg_mapstat.hip selects the order statistics from).
 // Both check on the device that they wrote what the offsets give them (ERR_PAIRS): the count
 // pass and the fill pass must agree, and a row that disagrees cannot write outside its slots.
 #include <climits>
@@ -38,6 +40,8 @@ struct PairArgs {
   const uint64_t* off;  // bg_result::poff
   int64_t* ref_rows;    // null: skipped
   int64_t* map_rows;
+  const double* SC;     // the map table's scores and, at every pair's slot, the member's score
+  double* vals;         //   (bg_pairs_scores, for bg_mapstat.hip); null: skipped
   bg_dstatus* st;
 };
 
@@ -140,6 +144,7 @@ __global__ void __launch_bounds__(BG_NT) k_pairs_flat(PairArgs A) {
       if (k < room) {  // (a fill that disagrees with the count stays inside the workgroup's slots)
         if (A.ref_rows) A.ref_rows[obase + k] = (int64_t)(r0 + j);
         if (A.map_rows) A.map_rows[obase + k] = (int64_t)m;
+        if (A.vals) A.vals[obase + k] = A.SC[m];
       }
     }
     run += all;
@@ -208,6 +213,7 @@ __global__ void __launch_bounds__(BG_NT) k_pairs_rows(PairArgs A) {
     if (j < room) {  // (a fill that disagrees with the count stays inside the row's slots)
       if (A.ref_rows) A.ref_rows[o + j] = (int64_t)r;
       if (A.map_rows) A.map_rows[o + j] = (int64_t)m;
+      if (A.vals) A.vals[o + j] = A.SC[m];
     }
     ++j;
   });
@@ -257,6 +263,49 @@ extern "C" int bg_result_map_pairs(bg_ctx* c, bg_result* r, uint64_t* total) {
   return 0;
 }
 
+// the fill: one launch on ctx's stream that writes, at every pair's slot, whichever of the
+// columns is asked for; r->poff is there (bg_result_map_pairs) and the total is not 0. The
+// status word is cleared before and read by bg_pairs_status
+static int pairs_fill(bg_ctx* c, bg_result* r, int64_t* ref_rows, int64_t* map_rows, double* vals) {
+  const bg_table* R = r->set->t[r->tab];
+  const bg_table* M = r->set->t[r->map_tab];
+  PairArgs A;
+  A.RS = R->ks, A.RE = R->ke, A.nr = r->n;
+  A.MS = M->ks, A.ME = M->ke, A.nm = M->n;
+  A.crit = r->mopts.faster ? BG_OVR_FAST : r->mopts.criterion;  // --faster: the deque is the window
+  A.ovr = (int64_t)r->mopts.overlap_bp;
+  A.range = (int64_t)r->mopts.range_bp;
+  A.perc = r->perc;
+  A.L = r->win_L, A.touch = r->win_touch;
+  A.wlo = r->wlo, A.whi = r->whi;
+  A.zin = r->zin, A.zout = r->zout;
+  A.lrows = r->lrows;
+  A.off = r->poff;
+  A.ref_rows = ref_rows, A.map_rows = map_rows;
+  A.SC = M->score, A.vals = vals;
+  A.st = c->dstat;
+  BG_HIP(c, hipMemsetAsync(&c->dstat->first_bad, 0xff, 8, c->stream));
+  const dim3 g(bg_blocks(r->n, BG_NT)), b(BG_NT);
+  if (A.lrows.ncls > 16) BG_LAUNCH(c, "k_pairs_rows", k_pairs_rows<BG_LONG_MAXC>, g, b, A);
+  else if (A.lrows.ncls > 4) BG_LAUNCH(c, "k_pairs_rows", k_pairs_rows<16>, g, b, A);
+  else if (A.lrows.ncls) BG_LAUNCH(c, "k_pairs_rows", k_pairs_rows<4>, g, b, A);
+  else BG_LAUNCH(c, "k_pairs_flat", k_pairs_flat, g, b, A);
+  BG_HIP(c, hipGetLastError());
+  return 0;
+}
+int bg_pairs_scores(bg_ctx* c, bg_result* r, double* vals) {
+  if (!r->set->t[r->map_tab]->score) return bg_fail(c, BG_E_INTERNAL, "pairs: the map table has no scores");
+  return pairs_fill(c, r, nullptr, nullptr, vals);
+}
+int bg_pairs_status(bg_ctx* c) {
+  BG_HIP(c, hipMemcpyAsync(c->hstat, c->dstat, sizeof(bg_dstatus), hipMemcpyDeviceToHost, c->stream));
+  BG_HIP(c, hipStreamSynchronize(c->stream));
+  if (c->hstat->first_bad != ~0ULL)
+    return bg_fail(c, BG_E_INTERNAL, "pairs: reference row " + std::to_string(c->hstat->first_bad >> 8) +
+                                         " on: another number of members written than counted");
+  return 0;
+}
+
 extern "C" int bg_result_export_map_pairs(bg_ctx* c, bg_result* r, int64_t* offsets, int64_t* ref_rows,
                                           int64_t* map_rows, uint64_t cap) {
   if (!c || !r) return BG_E_ARG;
@@ -275,34 +324,8 @@ extern "C" int bg_result_export_map_pairs(bg_ctx* c, bg_result* r, int64_t* offs
     BG_HIP(c, hipGetLastError());
   }
   if (!fill || !total) return 0;
-  const bg_table* R = r->set->t[r->tab];
-  const bg_table* M = r->set->t[r->map_tab];
-  PairArgs A;
-  A.RS = R->ks, A.RE = R->ke, A.nr = r->n;
-  A.MS = M->ks, A.ME = M->ke, A.nm = M->n;
-  A.crit = r->mopts.faster ? BG_OVR_FAST : r->mopts.criterion;  // --faster: the deque is the window
-  A.ovr = (int64_t)r->mopts.overlap_bp;
-  A.range = (int64_t)r->mopts.range_bp;
-  A.perc = r->perc;
-  A.L = r->win_L, A.touch = r->win_touch;
-  A.wlo = r->wlo, A.whi = r->whi;
-  A.zin = r->zin, A.zout = r->zout;
-  A.lrows = r->lrows;
-  A.off = r->poff;
-  A.ref_rows = ref_rows, A.map_rows = map_rows;
-  A.st = c->dstat;
-  BG_HIP(c, hipMemsetAsync(&c->dstat->first_bad, 0xff, 8, c->stream));
-  const dim3 g(bg_blocks(r->n, BG_NT)), b(BG_NT);
-  if (A.lrows.ncls > 16) BG_LAUNCH(c, "k_pairs_rows", k_pairs_rows<BG_LONG_MAXC>, g, b, A);
-  else if (A.lrows.ncls > 4) BG_LAUNCH(c, "k_pairs_rows", k_pairs_rows<16>, g, b, A);
-  else if (A.lrows.ncls) BG_LAUNCH(c, "k_pairs_rows", k_pairs_rows<4>, g, b, A);
-  else BG_LAUNCH(c, "k_pairs_flat", k_pairs_flat, g, b, A);
-  BG_HIP(c, hipGetLastError());
-  BG_HIP(c, hipMemcpyAsync(c->hstat, c->dstat, sizeof(bg_dstatus), hipMemcpyDeviceToHost, c->stream));
-  BG_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->hstat->first_bad != ~0ULL)
-    return bg_fail(c, BG_E_INTERNAL, "pairs: reference row " + std::to_string(c->hstat->first_bad >> 8) +
-                                         " on: another number of members written than counted");
+  if ((rc = pairs_fill(c, r, ref_rows, map_rows, nullptr))) return rc;
+  if ((rc = bg_pairs_status(c))) return rc;
   bg_mark(c, "pairs");
   return 0;
 }

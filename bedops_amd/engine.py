@@ -58,13 +58,17 @@ SYMBOLS = ["bg_open", "bg_close", "bg_last_error", "bg_sync", "bg_stream", "bg_b
            "bg_device_alloc", "bg_file_image_copy", "bg_copy_order", "bg_copy_fence",
            "bg_live", "bg_fail_alloc_after", "bg_load_columns", "bg_set_export_rows", "bg_result_kind",
            "bg_result_export_intervals", "bg_result_export_rows", "bg_result_export_map", "bg_sort_columns",
-           "bg_result_map_pairs", "bg_result_export_map_pairs", "bg_closest_rows", "bg_result_export_closest"]
+           "bg_result_map_pairs", "bg_result_export_map_pairs", "bg_closest_rows", "bg_result_export_closest",
+           "bg_result_export_map_values"]
 # what a result exports as columns (include/bedgpu.h BG_RESKIND_*)
 RESKIND_INTERVALS, RESKIND_ROWS, RESKIND_MAP, RESKIND_OTHER, RESKIND_CLOSEST = 0, 1, 2, 3, 4
 # the distance of a row that has no element on that side (include/bedgpu.h BG_DIST_NA)
 DIST_NA = -(1 << 63)
 # bedmap operations bg_result_export_map serves
 EXPORT_MAP_OPS = (1, 2, 3, 4, 5, 6)
+# bedmap operations bg_result_export_map_values serves: those, bases, bases-uniq, bases-uniq-f,
+# echo-ref-size, median, kth, variance, stdev, cv and mad
+EXPORT_MAP_VALUE_OPS = EXPORT_MAP_OPS + (7, 8, 9, 11, 19, 20, 21, 22, 23, 24)
 UID_BYTES = 128
 
 
@@ -210,6 +214,7 @@ def load_library():
     L.bg_result_export_rows.argtypes = [vp, vp, vp]
     L.bg_result_export_map.argtypes = [vp, vp, i32, vp]
     L.bg_sort_columns.argtypes = [vp, ctypes.POINTER(_Columns), vp, vp, vp, vp, vp]
+    L.bg_result_export_map_values.argtypes = [vp, vp, i32, vp]
     L.bg_result_map_pairs.argtypes = [vp, vp, ctypes.POINTER(u64)]
     L.bg_result_export_map_pairs.argtypes = [vp, vp, vp, vp, vp, u64]
     L.bg_closest_rows.argtypes = [vp, vp, i32, i32, i32, ctypes.POINTER(vp)]
@@ -343,6 +348,27 @@ class Result:
             return self.closest()
         else:
             raise BedgpuError(-6, "this result has no columnar form (text only)")
+        eng.sync()
+        return out
+
+    def values(self, op_index=None):
+        """a bedmap result's numeric operations as float64 torch tensors on the engine's device
+        (bg_result_export_map_values), one entry per reference row, NaN where the text has NAN:
+        the tensor of operation `op_index`, or with None a list with one tensor per operation in
+        EXPORT_MAP_VALUE_OPS and None for the others (text, --tmean, --wmean)."""
+        import torch
+        eng = self.eng
+        n, dev = self.rows(), eng.torch_device()
+
+        def one(q):
+            v = torch.empty(n, dtype=torch.float64, device=dev)
+            eng.sync_torch()
+            eng._check(eng.L.bg_result_export_map_values(eng.ctx, self.h, int(q), v.data_ptr() or None))
+            return v
+        if op_index is not None:
+            out = one(op_index)
+        else:
+            out = [one(q) if op in EXPORT_MAP_VALUE_OPS else None for q, op in enumerate(self.map_ops or [])]
         eng.sync()
         return out
 

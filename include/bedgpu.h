@@ -458,6 +458,42 @@ int bg_result_kind(const bg_result* res, int* kind, int* table);
 int bg_result_export_intervals(bg_ctx* ctx, bg_result* res, int32_t* chrom, int64_t* start, int64_t* end);
 int bg_result_export_rows(bg_ctx* ctx, bg_result* res, int64_t* rows);
 int bg_result_export_map(bg_ctx* ctx, bg_result* res, int op_index, double* values);
+/* Every numeric bedmap operation as a column: values (bg_result_rows doubles, caller-owned device
+ * memory, 16-byte aligned, written by kernels on ctx's stream) receives, per reference row, the
+ * double the formatter prints for mopts.ops[op_index], and NaN exactly where the text has NAN.
+ *   COUNT / INDICATOR / SUM / MEAN / MIN / MAX     as bg_result_export_map;
+ *   BASES / BASES_UNIQ / ECHO_SIZE                 the integer as a double (exact below 2^53);
+ *   BASES_UNIQ_F                                   (double)uniq / (double)(end - start): a
+ *                                                  zero-length row gives what that division gives;
+ *   VARIANCE / STDEV / CV                          the reference's double expressions on the
+ *                                                  running sums; NaN for fewer than 2 members, and
+ *                                                  for CV where the mean is 0;
+ *   MEDIAN / KTH                                   RollingKthAverage's rule on the sorted scores x
+ *                                                  of the n members: up = ceil(kth * n), down =
+ *                                                  floor(kth * n), each less 1 when > 0; (x[up] +
+ *                                                  x[up + 1]) / 2 when up == down, else x[up];
+ *   MAD                                            NaN for fewer than 2 members; else the median
+ *                                                  of |x - median| (the mean of the two middle
+ *                                                  ones for an even n) times op_arg (1 for <= 0).
+ * The value compares == to the formatter's; -0.0 and +0.0 are one value to the reference, and the
+ * sign of a zero result is not specified. The NaN that stands for NAN has its sign bit clear; a
+ * value that is itself a NaN (the text's "-nan": the square root of a variance that rounding took
+ * below zero, 0 / 0 for a zero-length reference row) has it set.
+ * BG_E_UNSUPPORTED (bg_last_error says why) for TMEAN / WMEAN (sums in the reference's
+ * heap-address order), the element and echo operations, ECHO_NAME and ECHO_REF_ROW_ID (text).
+ * BG_E_ARG for a result of another kind, an op_index outside the result's operations, a result
+ * built with skip_unmapped and a misaligned buffer; all of these before any launch.
+ * The operations up to CV: one launch, no host round trip. MEDIAN / KTH / MAD stand on the overlap
+ * join below, so they serve whatever it serves (text-loaded and column-loaded tables, every
+ * criterion, one file or two, --faster, zero-length rows): the members' scores are written at their
+ * pairs' slots and selected from there, per row, by counting for rows of a few members and by a
+ * wave-wide radix select for longer ones (BEDGPU_SEL_SMALL=<n> moves that limit, a test hook: 0
+ * selects every row by radix, a huge n every row by counting). They make the pair count's host
+ * round trip unless the caller ran bg_result_map_pairs before (the count then made is this call's
+ * temporary and not kept), and one more for the status: BG_E_INTERNAL if the fill wrote another
+ * number of members than counted. bg_live is the same after the call as before, also when it
+ * fails. Exporting values and formatting do not disturb each other, in either order. */
+int bg_result_export_map_values(bg_ctx* ctx, bg_result* res, int op_index, double* values);
 /* The overlap join behind a bedmap result: for reference row r, the rows of the map table in
  * S(r) (the rows --echo-map* would print), as indices into the map table, ascending. That is
  * table order, not the text route's order of equal rows by remainder or heap address, so it
