@@ -192,8 +192,8 @@ __device__ __forceinline__ bool fixed_digits(double v, int prec, uint64_t& N, bo
 
 // exact "%.{prec}e" of v (glibc: the binary value rounded half-to-even at prec+1
 // significant digits), for 1e-16 <= |v| < 2^128 (and 0); false outside that range.
-// N = round(|v| * 10^s) with s = prec - E must land in [10^prec, 10^(prec+1)); E starts
-// from log10 and is corrected by one step when the rounding says so.
+// N = round(|v| * 10^s) with s = prec - E, where floor(|v| * 10^s) must land in
+// [10^prec, 10^(prec+1)); E starts from log10 and is corrected by one step when it does not.
 __device__ __forceinline__ bool sci_digits(double v, int prec, uint64_t& N, int& E, bool& neg) {
   typedef unsigned __int128 u128;
   uint64_t bits = __double_as_longlong(v);
@@ -235,8 +235,15 @@ __device__ __forceinline__ bool sci_digits(double v, int prec, uint64_t& N, int&
     const u128 q = num / den, r = num - q * den;
     u128 qq = q;
     if (r * 2 > den || (r * 2 == den && (q & 1))) ++qq;
-    if (qq >= (u128)P * 10) { ++E; continue; }
-    if (qq < (u128)P) { --E; continue; }
+    // E is judged on the quotient before rounding: |v| < 10^E whose digits round up to
+    // 10^prec would otherwise pass as 1.00..e(E) where glibc prints 9.99..e(E-1)
+    if (q >= (u128)P * 10) { ++E; continue; }
+    if (q < (u128)P) { --E; continue; }
+    if (qq >= (u128)P * 10) {  // 9.99.. rounds up into the next decade: 1.00..e(E+1)
+      N = P;
+      ++E;
+      return true;
+    }
     N = (uint64_t)qq;
     return true;
   }

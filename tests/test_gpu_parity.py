@@ -354,8 +354,10 @@ def test_bedmap_decimal_score_spellings_vs_oracle(eng, oracle_bin):
     """the row parser's decimal fast path (parse_score_fast_ws: `<int>.<frac>` as one
     correctly rounded division) and every spelling it hands to the byte path: trailing zeros,
     integers written with a fraction, leading zeros, long fractions, 17-19 significant
-    digits (above 2^53: decimal_exact's 128-bit rounding), signs, exponents, a lone dot side;
-    byte-equal to the oracle for sums, means and extremes"""
+    digits (above 2^53: this load runs k_parse_rv, parse_score<false>, which lists them for
+    k_score_big; decimal_exact's 128-bit rounding is only in the wide parser and is run by
+    tests/test_gpu_decimal_roundtrip.py::test_loader_wide_route), signs, exponents, a lone
+    dot side; byte-equal to the oracle for sums, means and extremes"""
     spell = ["0.000", "12.000", "1.50", "007.25", "5.", ".5", "3.14159265358979", "0.1", "0.2",
              "0.3", "99.999", "123456789012.5", "1234567.123456789012", "12345678901.12345678",
              "-1.5", "+2.25", "1e3", "2.5e-2", "10.0001", "4503599627370497.5", "0.000001",
