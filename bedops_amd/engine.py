@@ -70,6 +70,8 @@ EXPORT_MAP_OPS = (1, 2, 3, 4, 5, 6)
 # echo-ref-size, median, kth, variance, stdev, cv and mad
 EXPORT_MAP_VALUE_OPS = EXPORT_MAP_OPS + (7, 8, 9, 11, 19, 20, 21, 22, 23, 24)
 UID_BYTES = 128
+# or'ed into bg_check's has_rest: bedmap --faster's nested-row check (include/bedgpu.h BG_CHECK_NEST)
+CHECK_NEST = 2
 
 
 class _CheckResult(ctypes.Structure):
@@ -707,14 +709,18 @@ class Engine:
             s.free()
 
     # -------------------------------------------------------------- --ec
-    def check(self, text, nfields=3, has_rest=False, name="-"):
+    def check(self, text, nfields=3, has_rest=False, name="-", nest=False, raw=False):
         """--ec validation of one input on the GPU (bg_check): None if it passes, else the
-        reference's exception text "in <name>\n<message>\nSee row: <n>"."""
+        reference's exception text "in <name>\n<message>\nSee row: <n>". nest: also bedmap
+        --faster's nested-row check (BG_CHECK_NEST). raw: return bg_check_result itself as a
+        dict (row, code, line_off, line_len, prev_off, prev_len; row 0 if the input passes)."""
         buf = ctypes.create_string_buffer(bytes(text), len(text) or 1)
         i = _Input(ctypes.cast(buf, ctypes.c_void_p), len(text), 0, BED3)
         r = _CheckResult()
-        self._check(self.L.bg_check(self.ctx, ctypes.byref(i), nfields, 1 if has_rest else 0,
-                                    ctypes.byref(r)))
+        flags = (1 if has_rest else 0) | (CHECK_NEST if nest else 0)
+        self._check(self.L.bg_check(self.ctx, ctypes.byref(i), nfields, flags, ctypes.byref(r)))
+        if raw:
+            return {k: int(getattr(r, k)) for k, _ in _CheckResult._fields_}
         if not r.row:
             return None
         line = bytes(text[r.line_off:r.line_off + r.line_len])

@@ -5,10 +5,13 @@
  * (interfaces/general-headers/data/bed/BedCheckIterator.hpp): lines read with getline
  * (Ext::ByLine, utility/ByLine.hpp), header lines skipped at the top (:215-228) and rejected
  * later (:238-246), check() (:326-593) field by field with the same marker loop, then the
- * order checks against the previous row and end > start (:594-624). Prints the exception
+ * order checks against the previous row and end > start (:594-624); with nest = 1 also
+ * bedmap --faster's nestCheck (:612-615): on the same chromosome, when no sort message was
+ * set, an end below maxEnd_ -- the previous row's end (:632) -- gives "Fully nested
+ * component found.", ahead of the end > start check. Prints the exception
  * text "in <file>\n<message>\nSee row: <n>" of the first failing line (nothing if the file
  * passes) and exits 1 / 0.
- * usage: ec_oracle <nfields> <has_rest 0|1> <file>
+ * usage: ec_oracle <nfields> <has_rest 0|1> <file> [nest 0|1]
  * Only used by tests/; never linked into the product.
  */
 #include <ctype.h>
@@ -17,7 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-static int NF, REST;
+static int NF, REST, NEST;
 static char MSG[4096];
 
 static int ucsc(const char* s, size_t n) {
@@ -165,9 +168,10 @@ static int check(const char* bl, size_t sz, row_t* R) {
 }
 
 int main(int argc, char** argv) {
-  if (argc != 4) return 2;
+  if (argc != 4 && argc != 5) return 2;
   NF = atoi(argv[1]);
   REST = atoi(argv[2]);
+  NEST = argc == 5 ? atoi(argv[4]) : 0;
   FILE* f = strcmp(argv[3], "-") ? fopen(argv[3], "rb") : stdin;
   if (!f) return 2;
   char* line = NULL;
@@ -207,6 +211,7 @@ int main(int argc, char** argv) {
               if (c2 < 0) strcpy(MSG, "Bed file not sorted by information following the 3rd column (columns 1-3 equal to previous row).");
             }
           }
+          if (!MSG[0] && NEST && R.end < L.end) strcpy(MSG, "Fully nested component found.");
         }
       }
       if (!MSG[0] && R.end <= R.start) strcpy(MSG, "End coordinates must be greater than start coordinates.");

@@ -1,5 +1,6 @@
 // CPU build of the GPU --ec grammar (bedops_amd/csrc/bg_check.h) over a file, with the same
-// first-failure rule as bg_check.hip: prints "in <file>\n<code>\nSee row: <n>" or nothing.
+// first-failure rule as bg_check.hip: prints "<row> <code> <line offset> <line length>" of the
+// first failing line, or nothing (nest = 1: bedmap --faster's nested-row check as well).
 // The message wording comes from bg_check_message() in the library; tests/test_check.py
 // maps codes to text with the same table through ctypes.
 #include <cstdio>
@@ -11,8 +12,8 @@
 #include "../../bedops_amd/csrc/bg_check.h"
 
 int main(int argc, char** argv) {
-  if (argc != 4) return 2;
-  const int nf = atoi(argv[1]), rest = atoi(argv[2]);
+  if (argc != 4 && argc != 5) return 2;  // <nfields> <has_rest> <file> [nest]
+  const int nf = atoi(argv[1]), rest = atoi(argv[2]), nest = argc == 5 ? atoi(argv[4]) : 0;
   FILE* f = fopen(argv[3], "rb");
   if (!f) return 2;
   std::string t;
@@ -43,7 +44,7 @@ int main(int argc, char** argv) {
       BgcRow P;
       const char* pl = t.data() + L[i - 1].first;
       if (bgc_line(pl, (uint32_t)L[i - 1].second, nf, rest, P) == BGC_OK)
-        err = bgc_order(pl, (uint32_t)L[i - 1].second, P, l, (uint32_t)L[i].second, R, rest);
+        err = bgc_order(pl, (uint32_t)L[i - 1].second, P, l, (uint32_t)L[i].second, R, rest, nest);
     } else if (R.end <= R.start) {
       err = BGC_END_LE_START;
     }

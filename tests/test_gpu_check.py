@@ -1,6 +1,11 @@
 """--ec through the drop-in CLIs on the GPU (bg_check): every error class of
 tests/test_check.py gives the oracle's message (oracle/ec_oracle.c) with the reference's
-error framing and exit status; clean files give the same output as without --ec."""
+error framing and exit status; clean files give the same output as without --ec.
+Every failing file here fits in one 8 KiB tile of bg_check.hip, mostly in one thread's 32
+bytes, and the large file is clean: what the kernels do across tiles, waves and threads (line
+numbers from the tile scan, lines and order checks that cross a seam, header blocks longer
+than a tile, which of several defects is reported, file ends, bg_check_result's spans, the
+nest check) is pinned by tests/test_gpu_check_tiles.py on the inputs of tests/ec_cases.py."""
 import os
 import subprocess
 
