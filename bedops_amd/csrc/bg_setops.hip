@@ -23,7 +23,7 @@
 //                         test (:1094-1096)
 // Memory access: every kernel reads its inputs coalesced. components() uses a
 // wave-striped layout (lane l of wave w handles rows w*W + k*64 + l) with 64-lane
-// max-scans and ballots; the merge-path kernels stage each 2048-element diagonal tile
+// max-scans and ballots; the merge-path kernels stage each 1024-element diagonal tile
 // of both inputs in LDS first. Count pass and write pass share one device function
 // (reduce-then-scan between them), so outputs are deterministic and exactly sized.
 #include <climits>
@@ -190,7 +190,7 @@ __global__ void k_mp_partition(const int64_t* __restrict__ XK, uint64_t nx,
 
 enum { MP_INTERSECT = 0, MP_DIFFERENCE = 1 };
 
-// One 2048-element diagonal tile of merge(X, Y). LDS holds X[i0-1 .. i1) then
+// One MP_TILE-element (1024) diagonal tile of merge(X, Y). LDS holds X[i0-1 .. i1) then
 // Y[j0-1 .. j1] (+1 for difference's "next O start"); sentinels outside the arrays.
 //   MP_INTERSECT : X, Y = component lists, keys = starts
 //   MP_DIFFERENCE: X = reference components (key start), Y = other components (key end)

@@ -108,6 +108,83 @@ def element_of(ref, comps, thres, use_pct, invert):
     return keep
 
 
+# ---------------------------------------------------------------- where things are
+# (tests/setop_cases.py places its inputs by these; tests/test_setop_cases.py checks them)
+def openings(iv):
+    """per row of a start-sorted list: does it open a component (k_components' flag)"""
+    out, run = [], None
+    for s, e in iv:
+        out.append(run is None or s > run)
+        run = e if run is None else max(run, e)
+    return out
+
+
+def merge_order(x, y, mode):
+    """the kernels' merged order of two component lists as [("x"|"y", index)], so that the
+    element at merged position d is merge_order(...)[d]. mode "i": k_mp_tile<MP_INTERSECT>, by
+    start, ties Y first; "d": k_mp_tile<MP_DIFFERENCE>, X start against Y end, ties Y first;
+    "u": k_merge_sorted, by start, ties X first"""
+    yk = 1 if mode == "d" else 0
+    i = j = 0
+    out = []
+    while i < len(x) or j < len(y):
+        if i < len(x) and (j >= len(y) or (x[i][0] <= y[j][yk] if mode == "u" else x[i][0] < y[j][yk])):
+            out.append(("x", i)); i += 1
+        else:
+            out.append(("y", j)); j += 1
+    return out
+
+
+def pieces_by_position(x, y, mode):
+    """[(d, piece)]: the piece the element at merged position d emits (at most one), as one
+    thread step of k_mp_tile computes it; mode "i" or "d". In order of d this is intersect2 /
+    difference2."""
+    out = []
+    i = j = 0
+    for d, (w, k) in enumerate(merge_order(x, y, mode)):
+        if mode == "i":
+            if w == "x":
+                (s, e), pend = x[k], (y[j - 1][1] if j else None)
+                i += 1
+            else:
+                (s, e), pend = y[k], (x[i - 1][1] if i else None)
+                j += 1
+            if pend is not None and min(e, pend) > s:
+                out.append((d, (s, min(e, pend))))
+        elif w == "x":
+            a, b = x[k]
+            qs = y[j][0] if j < len(y) else None  # the first O ending after a
+            if qs is None or qs >= b:
+                out.append((d, (a, b)))
+            elif qs > a:
+                out.append((d, (a, qs)))
+            i += 1
+        else:
+            if i > 0:
+                oe, rb = y[k][1], x[i - 1][1]
+                if rb > oe:
+                    out.append((d, (oe, min(rb, y[k + 1][0]) if k + 1 < len(y) else rb)))
+            j += 1
+    return out
+
+
+def segment_counts(x, y, mode, tile):
+    """pieces per merge-path tile of `tile` merged elements (a segmented result's seg counts)"""
+    cnt = [0] * ((len(x) + len(y) + tile - 1) // tile)
+    for d, _ in pieces_by_position(x, y, mode):
+        cnt[d // tile] += 1
+    return cnt
+
+
+def element_range(block, comps):
+    """(blo, bhi) of one k_element_flags block of reference rows: the first component ending
+    after the block's first start, and the first one starting at or after its largest end"""
+    import bisect
+    blo = bisect.bisect_right([c[1] for c in comps], block[0][0])
+    bhi = bisect.bisect_left([c[0] for c in comps], max(e for _, e in block))
+    return blo, max(blo, bhi)
+
+
 def intersect_zero_len(files):
     """--intersect including nextIntersectLine's zero-length prints (Bedops.cpp:1105-1181),
     as k_zi_mark / k_zi_replay / k_zi_place compute it: the non-empty output is the set
